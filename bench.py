@@ -38,7 +38,9 @@ Accounting (what each number counts):
                                         vs 8 TB/s -- a normalised rate, not HBM utilisation: states stay in registers / LDS,
                                         the measured HBM traffic (`traffic`) is orders of magnitude below it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2-batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2-batch B] [--dump-outputs DIR]
+--dump-outputs DIR: rank 0 writes what its last timed step returned (see dump_outputs) so that two builds can be compared
+output for output; the inputs depend only on the arguments (fixed network seed, fixed index range per step).
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU); this program itself
 uses no torch: RANK / WORLD_SIZE / MASTER_* are read by boolsi_amd.dist (TCP bootstrap + RCCL via the C-ABI).
 """
@@ -47,6 +49,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -57,6 +61,32 @@ BYTES_PER_NODE_UPDATE = 0.25    # read + write of the n-bit stat
 MAX_T = 4096
 PMC_FILE = os.path.join('profiles', 'r03_pmc.json')     # written by tools/pmc_read.py from the --pmc passes: top-level build
 PMC_FILE_LOWER = os.path.join('profiles', 'r03_pmc_lower.json')     # ... lower-level build
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def u32_limbs(words):
+    """unsigned integers (uint64 array, or Python ints up to 128 bits) -> float64 array of their 32-bit limbs, least
+    significant first: exact, where a float64 of a 64-bit key or count would round."""
+    if not isinstance(words, np.ndarray):
+        words = np.array([(int(words) >> (64 * i)) & (2 ** 64 - 1) for i in range(2)], dtype=np.uint64)
+    return np.stack([words & 0xFFFFFFFF, words >> 32], axis=-1).reshape(words.shape[:-1] + (2 * words.shape[-1],)).astype(np.float64)
+
+
+def dump_outputs(out_dir, r):
+    """What one bsx_run_attract2 call returned (an AttractResult), as DIR/<name>.npy in float64 32-bit limbs (u32_limbs):
+    attractor_<field>.npy, one row per attractor of the table (rows sorted by key: the engine returns them unordered),
+    n_no_attractor.npy and state_steps.npy (128-bit counts).  The table holds at most the engine's cap of 65536 rows."""
+    table = r.table
+    order = np.lexsort((table['length'],) + tuple(table['key'][:, w] for w in range(table['key'].shape[1])))
+    columns = {name: table[name][order] for name in table.dtype.names}
+    arrays = {'attractor_' + name: u32_limbs(c if c.ndim == 2 else c[:, None]) for name, c in columns.items()}
+    arrays['n_no_attractor'] = u32_limbs(r.n_no_attractor)
+    arrays['state_steps'] = u32_limbs(r.stats['state_steps'])
+    size = sum(a.nbytes for a in arrays.values())
+    assert size <= DUMP_LIMIT_BYTES, 'outputs of {} B exceed the dump limit'.format(size)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def main():
@@ -68,8 +98,12 @@ def main():
     ap.add_argument('--allow-socket-merge', action='store_true', help='N > 1: if RCCL cannot be set up, merge over the TCP control plane instead of failing')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--dump-table', metavar='PATH', help='rank 0 writes the merged attractor table of the timed steps there (JSON; tests)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='rank 0 writes the outputs of its last timed step there as <name>.npy '
+                                                          '(float64; see dump_outputs)')
     ap.add_argument('--cpu-log2-sample', type=int, default=25, help='log2 of the problems the CPU baseline runs (2^25: ~12 s on the box)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     from boolsi_amd import synth, _lib
     from boolsi_amd.attract import merge_tables, record_ints, table_from_merged
@@ -298,6 +332,8 @@ def main():
         if args.dump_table:
             with open(args.dump_table, 'w') as f:
                 json.dump({'{:x}'.format(k): [str(v) for v in e] for k, e in sorted(merged.items())}, f)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, results[-1])
         print(json.dumps(out))
     comm.barrier()
     comm.shutdown()
