@@ -24,8 +24,9 @@ constexpr uint64_t kProbeTile = 1ull << 22;     // lean tiles while the FAST len
 constexpr uint64_t kGeneralTile = 1ull << 32;   // problems per launch of the general kernel (32-bit offsets)
 constexpr double kLevelOverheadUs = 22.0;      // cascade: what one more level costs whatever its size (cost estimates)
 constexpr uint64_t kUnresCap = 1ull << 16;      // cascade: unresolved classes a level may list
-constexpr uint64_t kNearBytes = 1ull << 32;     // cascade: list of the classes a level hands to the level below (segments, and again
-                                                // packed: a 2^63 block of the north star lists 7.5e7 classes of 12 bytes at its top)
+constexpr uint64_t kNearBytes = 1ull << 32;     // cascade: list of the classes a level hands to the level below (segments, and two
+                                                // packed lists alternated by level, per side stream: a 2^63 block of the north star
+                                                // lists 7.5e7 classes of 12 bytes at its top)
 
 using MergedTable = std::unordered_map<Key8, WideRec, Key8Hash>;
 
@@ -591,13 +592,13 @@ uint32_t choose_top(const bsx_engine* h, const CascadeShape& sh, const std::vect
 // ---- one cube: the whole cascade as ONE chain of launches -----------------------------------------------------------
 // Level d of a block enumerates the assignments of the digits F^d still depends on (top level) or, below it, the digits
 // level d adds on top of every class the level above has listed as "near a cycle" (DESIGN.md "Deeper collapse").  How many
-// classes a level lists is only known on the device, so the chain is enqueued blind: k_compact_near packs the list and
-// writes its length into a LevelDesc, the next level's launch (full persistent grid) reads it there and sizes its own
-// work split.  Every level counts into its own Counters block; the host waits once -- for one chain, or for the chains of
-// all sub-blocks of a split block -- reads the blocks, and only then looks at what happened: a segment overflow (-> the
-// cube is redone from a shallower top), unresolved classes (attractors nobody has cached yet -> the detector runs from the
-// listed states; if one of them sat on a cycle the cube is repeated with the richer cache).  Passes are accepted or
-// discarded whole.
+// classes a level lists is only known on the device, so the chain is enqueued blind: the level's workgroups pack the list
+// themselves (each reserves a span of it on a LevelDesc's cursor, which after the launch is the list's length), the next
+// level's launch (full persistent grid) reads the length there and sizes its own work split.  Every level counts into its
+// own Counters block; the host waits once -- for one chain, or for the chains of all sub-blocks of a split block -- reads
+// the blocks, and only then looks at what happened: a segment overflow (-> the cube is redone from a shallower top),
+// unresolved classes (attractors nobody has cached yet -> the detector runs from the listed states; if one of them sat on a
+// cycle the cube is repeated with the richer cache).  Passes are accepted or discarded whole.
 struct ChainLevel {
     uint32_t depth = 0, k_bits = 0, r_here = 0, unit_shift = 0;
     bool per_parent = false;        // depth 1, evaluated per listed class (LeafProgram) instead of per child
@@ -685,8 +686,7 @@ int prepare_batch(bsx_handle h, const CascadeEnv& env, const std::vector<Chain*>
     if (B.n_side < 2) B.n_side = lists ? 1 : 0;
     for (uint32_t sl = 0; sl < B.n_side; ++sl) {
         HIPCHK(h, h->d_near_seg[sl].reserve((size_t)B.full.grid.x * B.seg_cap * (nw + 1)));      // (state + the tag of its cycle)
-        HIPCHK(h, h->d_near_counts[sl].reserve(B.full.grid.x));
-        HIPCHK(h, h->d_near_list[sl].reserve((size_t)B.full.grid.x * B.seg_cap * (nw + 1)));
+        for (auto& list : h->d_near_list[sl]) HIPCHK(h, list.reserve((size_t)B.full.grid.x * B.seg_cap * (nw + 1)));
         if (B.n_side > 1 && !h->side[sl]) HIPCHK(h, hipStreamCreateWithFlags(&h->side[sl], hipStreamNonBlocking));
     }
     HIPCHK(h, h->d_unres.reserve((size_t)std::max(blocks, 1u) * kUnresCap * rec_words));
@@ -695,15 +695,17 @@ int prepare_batch(bsx_handle h, const CascadeEnv& env, const std::vector<Chain*>
 }
 
 // The launches of one chain, enqueued on the handle's stream (nothing is waited for).
-// With side streams (B.n_side > 1) only the top level and the packing of its list run on the handle's stream; the lower levels
-// -- short launches that mostly wait on memory -- follow on side stream `slot`, next to the following chains' top levels.
+// With side streams (B.n_side > 1) only the top level runs on the handle's stream; the lower levels -- short launches that
+// mostly wait on memory -- follow on side stream `slot`, next to the following chains' top levels.
 // slot_busy[slot] = the event behind the last chain that used the slot's list buffers.
+// Level i reads the list d_near_list[slot][(i - 1) & 1] and writes d_near_list[slot][i & 1] (a level must not write into the
+// list it reads); the next level's length is the cursor in descriptor desc_base + i + 1, cleared by run_batch's fill.
 int enqueue_chain(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, const ChainBatch& B, Chain& ch, uint32_t slot,
                   std::vector<hipEvent_t>& slot_busy) {
     const uint32_t nw = h->net.nw, rec_words = nw + 3;
     const bool side = B.n_side > 1 && ch.top > 1;
     hipStream_t const main_st = h->stream, tail_st = side ? h->side[slot] : h->stream;
-    hipEvent_t* const ev = h->ev_chain.data() + 4 * (size_t)ch.index;       // top in, top out, hand-over, chain done
+    hipEvent_t* const ev = h->ev_chain.data() + 3 * (size_t)ch.index;       // top in, top out (= the hand-over), chain done
     if (side && slot_busy[slot]) HIPCHK(h, hipStreamWaitEvent(main_st, slot_busy[slot], 0));   // (the buffers' previous user has finished)
     AttractParams Q0 = env.P;
     Q0.cc.lds_slots = B.slots;
@@ -726,7 +728,8 @@ int enqueue_chain(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, c
         Q.stragglers = h->d_unres.p + (size_t)(ch.ctr_base + i) * kUnresCap * rec_words;
         Q.stragglers_cap = kUnresCap * rec_words;
         Q.near = l.depth > 1 ? h->d_near_seg[slot].p : nullptr;
-        Q.near_counts = l.depth > 1 ? h->d_near_counts[slot].p : nullptr;
+        Q.near_list = l.depth > 1 ? h->d_near_list[slot][i & 1].p : nullptr;
+        Q.level_out = l.depth > 1 ? h->d_level + ch.desc_base + i + 1 : nullptr;
         Q.near_cap = l.depth > 1 ? B.seg_cap : 0;
         dim3 grid = B.full.grid;
         if (i == 0) {
@@ -745,7 +748,7 @@ int enqueue_chain(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, c
             HIPCHK(h, hipEventRecord(ev[0], main_st));
         } else {
             Q.count = 0;
-            Q.entries = h->d_near_list[slot].p;         // (packed by the k_compact_near before this launch)
+            Q.entries = h->d_near_list[slot][(i - 1) & 1].p;    // (packed by the level above)
             Q.level_in = h->d_level + ch.desc_base + i;
             Q.chunk = 0; Q.chunk_first = 0;
             // the lower-level build of the kernel: no pool, no rings (its LDS is the tables alone)
@@ -765,17 +768,11 @@ int enqueue_chain(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, c
         hipStream_t const st = i == 0 ? main_st : tail_st;
         HIPCHK(h, launch_attract_pool((int)nw, (int)h->net.k_mux, h->lut_mode, grid, shmem_here, st, Q));
         if (i == 0) HIPCHK(h, hipEventRecord(ev[1], main_st));
-        if (l.depth > 1)
-            HIPCHK(h, launch_compact_near(h->d_near_seg[slot].p, h->d_near_counts[slot].p, grid.x, B.seg_cap, nw + 1, h->d_near_list[slot].p,
-                                          h->d_level + ch.desc_base + i + 1, st));
-        if (i == 0 && side) {                           // the rest of the chain: on the side stream, behind the list
-            HIPCHK(h, hipEventRecord(ev[2], main_st));
-            HIPCHK(h, hipStreamWaitEvent(tail_st, ev[2], 0));
-        }
+        if (i == 0 && side) HIPCHK(h, hipStreamWaitEvent(tail_st, ev[1], 0));     // the rest of the chain: on the side stream, behind the list
     }
     if (side) {
-        HIPCHK(h, hipEventRecord(ev[3], tail_st));
-        slot_busy[slot] = ev[3];
+        HIPCHK(h, hipEventRecord(ev[2], tail_st));
+        slot_busy[slot] = ev[2];
     }
     return BSX_OK;
 }
@@ -874,7 +871,7 @@ int run_batch(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, const
     }
     if (!n_live) return BSX_OK;
     if (blocks > kMaxChainBlocks || n_live > kMaxChains) return fail(h, BSX_ERR_INVALID, "internal: too many chains in one batch");
-    while (h->ev_chain.size() < 4 * (size_t)n_live) {
+    while (h->ev_chain.size() < 3 * (size_t)n_live) {
         hipEvent_t e = nullptr;
         HIPCHK(h, hipEventCreate(&e));
         h->ev_chain.push_back(e);
@@ -913,8 +910,8 @@ int run_batch(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, const
     for (Chain* ch : chains) {
         if (ch->lv.empty()) continue;
         float ms_top = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms_top, h->ev_chain[4 * ch->index], h->ev_chain[4 * ch->index + 1]));
-        tot.launches += 2 * ch->top - 1;
+        HIPCHK(h, hipEventElapsedTime(&ms_top, h->ev_chain[3 * ch->index], h->ev_chain[3 * ch->index + 1]));
+        tot.launches += ch->top;
         tot.dominant_ms += ms_top;
         tot.dominant_exec += h->h_ctr[ch->ctr_base].steps_exec;
         ++tot.dominant_launches;

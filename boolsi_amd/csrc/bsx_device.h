@@ -155,9 +155,10 @@ struct CycleCache {
     uint32_t lds_slots;         // power of two; the LDS mirror holds at most lds_slots / 2 states
 };
 
-// Hand-over between two levels of a cube cascade, written by k_compact_near, read by the next level's launch.
+// Hand-over between two levels of a cube cascade, written by the level above (its workgroups reserve their spans of the
+// packed list here), read by the next level's launch.
 struct LevelDesc {
-    unsigned long long n_entries;   // classes listed by the level above (packed list)
+    unsigned long long n_entries;   // classes listed by the level above (packed list): the cursor its workgroups reserve spans on
     unsigned int abort;             // a segment of the level above overflowed: the list is incomplete, the block is redone shallower
     unsigned int pad;
 };
@@ -232,16 +233,18 @@ struct AttractParams {
     // fresh stage makes `cube_depth` updates before the first lookup, and a class whose common state F^depth(x)
     // is a cached cycle state -- its members enter the cycle at different times <= depth -- is not accounted but
     // listed by its representative's initial state: workgroup g appends to its own segment near[g * near_cap ..]
-    // (near_cap states of nw words, a counter in LDS, no global atomics) and leaves its count in near_counts[g];
-    // k_compact_near then packs the segments into one list.  Counters::near_classes = the total, near_overflow =
-    // a segment was too small.  The host runs the listed classes again one level down:
+    // (near_cap entries of nw + 1 words, a counter in LDS, no global atomics); at its end it reserves a span of the packed
+    // list near_list with one atomic add on level_out->n_entries and copies its segment there (a segment that was too
+    // small sets level_out->abort).  Counters::near_classes = the total, near_overflow = a segment was too small.  The
+    // list must not be the one this level reads (entries).  The host runs the listed classes again one level down:
     // entries != null: work item i is sub-assignment i & (2^entry_shift - 1) of the digits this level adds,
     // on top of the state entries[(i >> entry_shift) * nw ..].
     uint32_t cube_depth;        // >= 1 (1 = one update, then lookups: the plain cube pass)
     uint32_t entry_shift;
     const uint32_t* entries;
     uint32_t* near;
-    uint32_t* near_counts;
+    uint32_t* near_list;
+    LevelDesc* level_out;
     uint64_t near_cap;
     // Work distribution of the pool kernel: wave w of the grid starts with [w * chunk_first, (w + 1) * chunk_first);
     // the shared cursor hands out what lies beyond n_waves * chunk_first, `chunk` at a time (chunk == 0: nothing

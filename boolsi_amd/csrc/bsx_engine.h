@@ -83,9 +83,8 @@ struct bsx_engine {
     size_t image_n = ~size_t(0);
     uint32_t image_slots = 0;
     // deep cube passes, one set per side stream (the lower levels of up to kSideStreams chains run side by side):
-    bsx::DevBuf<uint32_t> d_near_seg[bsx::kSideStreams];    // classes listed for the level below, one segment per workgroup,
-    bsx::DevBuf<uint32_t> d_near_counts[bsx::kSideStreams]; // the segments' fill counts,
-    bsx::DevBuf<uint32_t> d_near_list[bsx::kSideStreams];   // and the packed list the next level reads
+    bsx::DevBuf<uint32_t> d_near_seg[bsx::kSideStreams];        // classes listed for the level below, one segment per workgroup,
+    bsx::DevBuf<uint32_t> d_near_list[bsx::kSideStreams][2];    // and the packed lists, alternated by level (one is read, one written)
     hipStream_t side[bsx::kSideStreams] = {};
     bsx::DevBuf<uint32_t> d_unres;      // cascade: unresolved classes per level (state, t, member count)
     bsx::DevBuf<bsx::LeafProgram> d_leaf;   // cascade: the depth-1 level's per-parent program (bsx_device.h)
@@ -113,7 +112,7 @@ struct bsx_engine {
     bsx::DevBuf<uint32_t> d_any, d_fv, d_pv, d_set, d_clr;
 
     // counters: one block for a single pass, one per level for a cube cascade, which is enqueued as a whole and read
-    // back once.  The hand-over descriptors of the levels (k_compact_near -> next launch) sit right in front of block 0
+    // back once.  The hand-over descriptors of the levels (level above -> next launch) sit right in front of block 0
     // so that one fill clears both.  h_ctr: pinned host buffer of the same shape; a cascade's last kernel (k_publish)
     // stores the blocks there and then the sequence number of the call into h_flag, which the host spins on -- the
     // wake-up of a blocking wait was a third of a 0.3 ms call.

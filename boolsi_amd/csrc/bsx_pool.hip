@@ -1,40 +1,10 @@
 // Class-pool attract kernel: dispatch over the state width (the kernels are built per width in bsx_pool_nw*.hip),
-// the packing kernel between the levels of a cube cascade, and the kernel's LDS footprint.
+// the last kernel of a cube cascade, and the kernel's LDS footprint.
 #include "bsx_kernels_common.h"
 
 namespace bsx {
 
 constexpr int kPoolWaves = kPoolBlockThreads / 64;
-
-// ------------------------------------------------------------------------------------------------
-// Deep cube passes: the workgroups' segments of listed classes -> one contiguous list (block g copies segment g
-// to where the segments before it end), and the list's length -> the descriptor the next level's launch reads
-// (that launch is already enqueued: the host does not look at anything between the levels of a cascade).
-__global__ __launch_bounds__(256) void k_compact_near(const uint32_t* seg, const uint32_t* counts, uint32_t n_seg,
-                                                      uint64_t cap, uint32_t nw, uint32_t* out, LevelDesc* desc) {
-    __shared__ unsigned long long before;
-    const uint32_t listed = counts[blockIdx.x];
-    if (listed > cap && threadIdx.x == 0) atomicOr(&desc->abort, 1u);      // a segment was too small: the list is incomplete
-    if (listed == 0 && blockIdx.x != n_seg - 1) return;                    // (most segments of a short list)
-    if (threadIdx.x == 0) before = 0;
-    __syncthreads();
-    unsigned long long part = 0;
-    for (uint32_t g = threadIdx.x; g < blockIdx.x; g += blockDim.x) part += counts[g] < cap ? counts[g] : cap;
-    if (part) atomicAdd(&before, part);
-    __syncthreads();
-    const uint64_t mine = listed < cap ? listed : cap;
-    const uint32_t* src = seg + (uint64_t)blockIdx.x * cap * nw;
-    uint32_t* dst = out + before * nw;
-    for (uint64_t i = threadIdx.x; i < mine * nw; i += blockDim.x) dst[i] = src[i];
-    if (threadIdx.x == 0 && blockIdx.x == n_seg - 1) desc->n_entries = before + mine;
-}
-
-hipError_t launch_compact_near(const uint32_t* seg, const uint32_t* counts, uint32_t n_seg, uint64_t cap, uint32_t nw,
-                               uint32_t* out, LevelDesc* desc, hipStream_t stream) {
-    if (!n_seg) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_compact_near, dim3(n_seg), dim3(256), 0, stream, seg, counts, n_seg, cap, nw, out, desc);
-    return hipGetLastError();
-}
 
 // Last kernel of a chain: the counter blocks -> pinned host memory, then (system-scope release) the sequence number
 // the host is spinning on (bsx_attract_api.cpp: fetch_counters).

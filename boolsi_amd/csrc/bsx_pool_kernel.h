@@ -107,19 +107,13 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
                 // per-parent level: the children of a batch of 64 parents are shared out over `parts` work items (below)
                 if (P.leaf && n_items) n_items = ((listed + 63ull) & ~63ull) * leaf_parts(P.leaf->kb, listed, (uint64_t)gridDim.x * kPoolWaves);
             }
-            if (n_items == 0) {                             // nothing was handed down (or the level above overflowed)
-                if (threadIdx.x == 0 && P.near_counts) P.near_counts[blockIdx.x] = 0;
-                return;
-            }
+            if (n_items == 0) return;                       // nothing was handed down (or the level above overflowed)
             const uint64_t n_waves = (uint64_t)gridDim.x * kPoolWaves;
             if (n_items < (1ull << 28)) { chunk_first = ((n_items + n_waves - 1) / n_waves + 63) / 64 * 64; chunk = 0; }
             else { chunk_first = 4096; chunk = 4096; }
             // a short list keeps only some workgroups busy (wave w of workgroup g takes share w * gridDim.x + g, so those are
-            // spread over the chip): the others leave before they stage anything
-            if ((uint64_t)blockIdx.x * chunk_first >= n_items) {
-                if (threadIdx.x == 0 && P.near_counts) P.near_counts[blockIdx.x] = 0;
-                return;
-            }
+            // spread over the chip): the others leave before they stage anything (and reserve nothing in the next list)
+            if ((uint64_t)blockIdx.x * chunk_first >= n_items) return;
         }
     }
     if constexpr (CUBE) {
@@ -1094,14 +1088,25 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
         const unsigned long long w_exec = wave_sum((unsigned long long)nexec);
         if (lane == 0 && w_exec) atomicAdd(&wg_ctr[3], w_exec);
     }
-    __syncthreads();
+    // (the waves' stores into the segment of listed classes, too, are made visible to the whole workgroup here: the copy below
+    // reads entries other waves wrote -- a workgroup-scope release by every wave, the barrier, a workgroup-scope acquire)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     if (threadIdx.x == 0) {
         if constexpr (cube) {
-            if (P.near_counts) {
+            BSX_RARE_PARAMS(Pr);
+            if (Pr->level_out) {
+                // the workgroup's span of the next level's list: one cursor for the whole grid, which after this launch
+                // holds the list's length (stream order makes it visible to the next level's launch)
                 const uint32_t listed = lc[2];
-                P.near_counts[blockIdx.x] = listed;
+                const uint32_t mine = listed < Pr->near_cap ? listed : (uint32_t)Pr->near_cap;
+                lc[1] = mine ? (uint32_t)atomicAdd(&Pr->level_out->n_entries, (unsigned long long)mine) : 0u;     // (lc[1]: free by now)
                 if (listed) atomicAdd(&P.ctr->near_classes, (unsigned long long)listed);
-                if (listed > P.near_cap) atomicOr(&P.ctr->near_overflow, 1u);
+                if (listed > Pr->near_cap) {            // the segment was too small: the list is incomplete
+                    atomicOr(&Pr->level_out->abort, 1u);
+                    atomicOr(&P.ctr->near_overflow, 1u);
+                }
             }
         }
         const unsigned long long ref = wg_ctr[2] + (P.cap_rel_inf ? 0ull : wg_ctr[1] * P.max_t);
@@ -1109,6 +1114,17 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
         if (wg_ctr[3]) atomicAdd(&P.ctr->steps_exec, wg_ctr[3]);
         if (wg_ctr[0]) atomicAdd(&P.ctr->n_none, wg_ctr[0]);
         if constexpr (cube) atomicMax(&P.ctr->t_last, (unsigned long long)wall_clock64());
+    }
+    if constexpr (cube) {
+        BSX_RARE_PARAMS(Pr);
+        if (Pr->level_out) {                                // uniform
+            __syncthreads();                                // (lc[1] from thread 0)
+            const uint32_t listed = lc[2], base = lc[1];
+            const uint64_t words = (uint64_t)(listed < Pr->near_cap ? listed : (uint32_t)Pr->near_cap) * (NW + 1);
+            const uint32_t* src = Pr->near + (uint64_t)blockIdx.x * Pr->near_cap * (NW + 1);
+            uint32_t* dst = Pr->near_list + (uint64_t)base * (NW + 1);
+            for (uint64_t i = threadIdx.x; i < words; i += kPoolBlock) dst[i] = src[i];
+        }
     }
 }
 

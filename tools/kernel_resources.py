@@ -38,7 +38,6 @@ LAUNCHED = {
     'bsx::k_simulate_sliced64<4, 3, true>': 'config 5 (n = 128, K = 3 simulate) with digests',
     'bsx::k_simulate_sliced64<4, 3, false>': 'config 5, final states only',
     'bsx::k_attract<2, 3, 1>': 'chaotic K = 3 networks (n = 64): every trajectory through the detector',
-    'bsx::k_compact_near': 'cube cascade: packing between levels',
     'bsx::k_publish': 'cube cascade: counters to the host',
 }
 
