@@ -11,6 +11,10 @@ import ctypes as C
 import numpy as np
 
 MAX_WORDS = 4
+MAX_STATE_WORDS = 16        # BSX_MAX_STATE_WORDS: keys of the wide-state family (n <= BSX_MAX_NODES_WIDE)
+MAX_NODES = 256
+MAX_NODES_WIDE = 1024
+LUT_WIDE = 3                # bsx_network_info's lut_mode for a network lowered to the wide-state family
 T_INF = 2 ** 64 - 1
 
 LIB_NAME = os.environ.get('BSX_LIB', 'libbsx_hip.so')      # (BSX_LIB=libbsx_hip_diag.so: diagnostic build, tools only)
@@ -18,7 +22,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 EXPORTS = (
     'bsx_create', 'bsx_destroy', 'bsx_last_error', 'bsx_status_string', 'bsx_device_info', 'bsx_network_info',
-    'bsx_set_network', 'bsx_set_problem_space', 'bsx_run_attract', 'bsx_run_attract2', 'bsx_run_attract_fgraph', 'bsx_run_target',
+    'bsx_set_network', 'bsx_set_problem_space', 'bsx_run_attract', 'bsx_run_attract2', 'bsx_run_attract_wide', 'bsx_run_attract_fgraph', 'bsx_run_target',
     'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_synchronize',
     'bsx_comm_unique_id', 'bsx_comm_init', 'bsx_comm_allgather', 'bsx_comm_destroy',
 )
@@ -86,6 +90,9 @@ ATTR_REC = np.dtype([('key', '<u8', (MAX_WORDS,)), ('length', '<u8'), ('count', 
 # bsx_attr_rec2: count 128, sum_l 192, sum_l2 256 bits, little-endian 64-bit words
 ATTR_REC2 = np.dtype([('key', '<u8', (MAX_WORDS,)), ('length', '<u8'), ('count', '<u8', (2,)), ('sum_l', '<u8', (3,)),
                       ('sum_l2', '<u8', (4,))])
+# bsx_attr_rec2w: ATTR_REC2 with BSX_MAX_STATE_WORDS key words (bsx_run_attract_wide)
+ATTR_REC2W = np.dtype([('key', '<u8', (MAX_STATE_WORDS,)), ('length', '<u8'), ('count', '<u8', (2,)),
+                       ('sum_l', '<u8', (3,)), ('sum_l2', '<u8', (4,))])
 PROBLEM_REC = np.dtype([('key', '<u8', (MAX_WORDS,)), ('length', '<u8'), ('trajectory_l', '<u8'),
                         ('found', '<u4'), ('pad', '<u4')])
 HIT = np.dtype([('offset', '<u8'), ('t', '<u8')])
@@ -125,6 +132,8 @@ def load():
                                     C.POINTER(u64), vp, C.POINTER(Stats)]
     lib.bsx_run_attract2.argtypes = [vp, U128, U128, u64, u64, vp, u32, C.POINTER(u32), C.POINTER(U128),
                                      C.POINTER(Stats2)]
+    lib.bsx_run_attract_wide.argtypes = [vp, U128, U128, u64, u64, vp, u32, C.POINTER(u32), C.POINTER(U128),
+                                         C.POINTER(Stats2)]
     lib.bsx_run_attract_fgraph.argtypes = [vp, C.POINTER(Index), u64, u64, u64, vp, u32, C.POINTER(u32),
                                            C.POINTER(u64), C.POINTER(Stats)]
     lib.bsx_run_target.argtypes = [vp, C.POINTER(Index), u64, u64, vp, vp, vp, u64, C.POINTER(u64),

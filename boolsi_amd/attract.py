@@ -74,7 +74,9 @@ def merge_tables(tables):
                                                       ('key', 'length', 'count', 'sum_l', 'sum_l2_lo', 'sum_l2_hi'))))
             recs = []
             for r in rows:
-                key = r[0][0] | r[0][1] << 64 | r[0][2] << 128 | r[0][3] << 192
+                key = 0
+                for w, x in enumerate(r[0]):
+                    key |= x << (64 * w)
                 if wide:
                     recs.append((key, r[1], r[2][0] | r[2][1] << 64, r[3][0] | r[3][1] << 64 | r[3][2] << 128,
                                  r[4][0] | r[4][1] << 64 | r[4][2] << 128 | r[4][3] << 192))
@@ -101,7 +103,9 @@ def table_from_merged(merged, dtype):
     out = np.zeros(len(merged), dtype)
     wide = 'sum_l2' in dtype.names
     for i, (key, (length, count, s1, s2)) in enumerate(sorted(merged.items())):
-        for w in range(4):
+        if key >> (64 * len(out[i]['key'])):
+            raise OverflowError('key does not fit {} words'.format(len(out[i]['key'])))
+        for w in range(len(out[i]['key'])):
             out[i]['key'][w] = (key >> (64 * w)) & m64
         out[i]['length'] = length
         if wide:
@@ -128,7 +132,8 @@ def run_attract_range(engine, first, count, max_t=inf, max_attractor_l=inf, cap=
     done = 0
     while done < count:
         piece = min(count - done, 1 << 127)
-        r = engine.attract2(first + done, piece, max_t, max_attractor_l, cap=cap)
+        run = engine.attract_wide if getattr(engine, 'wide', False) else engine.attract2     # (networks beyond 256 nodes)
+        r = run(first + done, piece, max_t, max_attractor_l, cap=cap)
         merged_tables.append(r.table)
         none += r.n_no_attractor
         for k in stats:
@@ -160,7 +165,7 @@ def attract_master(engine, origin_simulation_problem, simulation_problem_variati
 
     if comm.active:
         from . import _lib
-        tables = comm.allgather_records(table_from_merged(merged, _lib.ATTR_REC2))
+        tables = comm.allgather_records(table_from_merged(merged, _lib.ATTR_REC2W if getattr(engine, 'wide', False) else _lib.ATTR_REC2))
         merged = merge_tables(tables)
         none, steps, execd = comm.allreduce_sum_int([none, stats['state_steps'], stats['executed_steps']])
         stats['state_steps'], stats['executed_steps'] = steps, execd

@@ -16,7 +16,7 @@ import numpy as np
 
 from .constants import RANGE_CODE
 
-MAX_NODES = 256           # BSX_MAX_NODES
+MAX_NODES = 1024          # BSX_MAX_NODES_WIDE (beyond BSX_MAX_NODES = 256: the wide-state family)
 MAX_PREDECESSORS = 24     # BSX_MAX_PREDECESSORS (2^24-bit table = 2 MiB per node)
 
 

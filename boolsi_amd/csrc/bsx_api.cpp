@@ -119,6 +119,7 @@ extern "C" int bsx_destroy(bsx_handle h) {
     if (h->ev_top1) (void)hipEventDestroy(h->ev_top1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->h_ctr) (void)hipHostFree(h->h_ctr);
+    wide_release(h);
     delete h;
     return BSX_OK;
 }
@@ -155,7 +156,9 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     if (!h) return BSX_ERR_INVALID;
     if (n_nodes == 0 || !pred_offsets || !tt_word_offsets || !tt_words)
         return fail(h, BSX_ERR_INVALID, "bsx_set_network: null table or zero nodes");
-    if (n_nodes > BSX_MAX_NODES) return fail(h, BSX_ERR_UNSUPPORTED, "more than BSX_MAX_NODES nodes");
+    if (n_nodes > BSX_MAX_NODES || wide_forced())          // the wide-state family (bsx_wide_api.cpp)
+        return wide_set_network(h, n_nodes, pred_offsets, pred_idx, tt_word_offsets, tt_words);
+    wide_release(h);
     HIPCHK(h, hipSetDevice(h->device));
     h->have_net = false;
     h->have_space = false;
@@ -294,6 +297,9 @@ extern "C" int bsx_set_problem_space(bsx_handle h, const uint64_t* origin_state_
     if (!origin_state_words) return fail(h, BSX_ERR_INVALID, "origin state is null");
     if (n_pert_var > BSX_MAX_PERT_VARIATIONS) return fail(h, BSX_ERR_UNSUPPORTED, "more than BSX_MAX_PERT_VARIATIONS perturbation variations");
     if (n_any > h->n_nodes) return fail(h, BSX_ERR_INVALID, "more 'any' nodes than nodes");
+    if (h->wide)
+        return wide_set_problem_space(h, origin_state_words, any_nodes, n_any, fixed, n_fixed, fixed_var, n_fixed_var,
+                                      sched, n_sched, pert_var, n_pert_var);
     HIPCHK(h, hipSetDevice(h->device));
     h->have_space = false;
     const uint32_t n = h->n_nodes, nw = h->net.nw;
@@ -518,6 +524,30 @@ extern "C" int bsx_run_target(bsx_handle h, const bsx_index* first, uint64_t cou
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (count == 0) return BSX_OK;
     if (count > (1ull << 32)) return fail(h, BSX_ERR_INVALID, "at most 2^32 problems per call");
+    if (h->wide) {
+        // per-problem first-hit times of the wide kernel, listed here (chunks of 2^24 problems)
+        uint64_t total = 0;
+        bsx_stats part{};
+        if (stats) stats->problems = count;
+        for (uint64_t done = 0; done < count; done += 1ull << 24) {
+            const uint64_t m = std::min<uint64_t>(1ull << 24, count - done);
+            const bsx_index at = index_plus(*first, done, h->sp.n_any);
+            std::vector<uint32_t> t_hit;
+            if (int rc = wide_target_times(h, &at, m, max_t, mask_words, code_words, t_hit, &part)) return rc;
+            for (uint64_t p = 0; p < m; ++p) {
+                if (t_hit[p] == 0xFFFFFFFFu) continue;
+                if (total == cap) return fail(h, BSX_ERR_TABLE_FULL, "more hits than the caller's capacity (bsx_run_target_summary counts without listing)");
+                hits[total++] = bsx_hit{done + p, t_hit[p]};
+            }
+            if (stats) {
+                stats->state_steps += part.state_steps; stats->executed_steps += part.executed_steps;
+                stats->kernel_ms += part.kernel_ms; stats->kernel_launches += part.kernel_launches;
+            }
+        }
+        *n_hits = total;
+        if (stats) stats->total_ms = now_ms() - t_begin;
+        return BSX_OK;
+    }
     DevBuf<uint32_t> d_thit;
     HIPCHK(h, d_thit.alloc(count));
     Counters ctr{};
@@ -558,6 +588,32 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (count == 0) return BSX_OK;
     if (count > (1ull << 40)) return fail(h, BSX_ERR_INVALID, "at most 2^40 problems per call");
+    if (h->wide) {
+        // per-problem first-hit times of the wide kernel, summarised here (chunks of 2^24 problems)
+        uint64_t total = 0, listed = 0;
+        bsx_stats part{};
+        if (stats) stats->problems = count;
+        for (uint64_t done = 0; done < count; done += 1ull << 24) {
+            const uint64_t m = std::min<uint64_t>(1ull << 24, count - done);
+            const bsx_index at = index_plus(*first, done, h->sp.n_any);
+            std::vector<uint32_t> t_hit;
+            if (int rc = wide_target_times(h, &at, m, max_t, mask_words, code_words, t_hit, &part)) return rc;
+            for (uint64_t p = 0; p < m; ++p) {
+                if (t_hit[p] == 0xFFFFFFFFu) continue;
+                ++total;
+                if (hist_bins) ++hist[std::min<uint64_t>(t_hit[p], hist_bins - 1)];
+                if (listed < cap) hits[listed++] = bsx_hit{done + p, t_hit[p]};
+            }
+            if (stats) {
+                stats->state_steps += part.state_steps; stats->executed_steps += part.executed_steps;
+                stats->kernel_ms += part.kernel_ms; stats->kernel_launches += part.kernel_launches;
+            }
+        }
+        *n_hits = total;
+        if (n_listed) *n_listed = listed;
+        if (stats) stats->total_ms = now_ms() - t_begin;
+        return BSX_OK;
+    }
 
     DevBuf<unsigned long long> d_hist;              // (one bin even if the caller wants none: the kernels count into it)
     HIPCHK(h, d_hist.alloc(std::max<uint32_t>(hist_bins, 1)));
@@ -872,6 +928,7 @@ extern "C" int bsx_run_simulate(bsx_handle h, const bsx_index* first, uint64_t c
     if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
     if (int rc = check_range(h, first, count)) return rc;
     if (int rc = check_max_t(h, max_t)) return rc;
+    if (h->wide) return wide_run_simulate(h, first, count, max_t, trajectories, final_states, digests, stats);
     // Long fixed-length runs that only want final states go through the bit-sliced kernel
     // (BSX_SLICED=0 forces the per-lane kernel, for A/B runs and tests).
     const char* sl_env = std::getenv("BSX_SLICED");
@@ -899,5 +956,6 @@ extern "C" int bsx_run_trajectories(bsx_handle h, const bsx_index* first, const 
         words = std::max(words, out_offsets[q] + (t_len[q] + 1) * h->w64);
         tmax = std::max(tmax, t_len[q]);
     }
+    if (h->wide) return wide_run_trajectories(h, first, offsets, t_len, n, out, out_offsets, stats);
     return run_sim_common(h, first, n, tmax, offsets, t_len, out_offsets, words, out, nullptr, nullptr, stats);
 }

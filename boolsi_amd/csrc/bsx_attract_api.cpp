@@ -1486,6 +1486,7 @@ extern "C" int bsx_run_attract(bsx_handle h, const bsx_index* first, uint64_t co
                                uint64_t max_len, bsx_attr_rec* table, uint32_t cap, uint32_t* n_out,
                                uint64_t* n_no_attractor, bsx_problem_rec* per_problem, bsx_stats* stats) {
     if (!h) return BSX_ERR_INVALID;
+    if (h->wide) return fail(h, BSX_ERR_UNSUPPORTED, "networks of the wide-state family (more than BSX_MAX_NODES nodes, or BSX_WIDE=1): use bsx_run_attract_wide");
     if (!table || !n_out) return fail(h, BSX_ERR_INVALID, "table / n_out is null");
     if (int rc = attract_preamble(h, first, count, max_t)) return rc;
     const double t_begin = now_ms();
@@ -1527,6 +1528,7 @@ extern "C" int bsx_run_attract2(bsx_handle h, bsx_u128 first_flat, bsx_u128 coun
                                 bsx_attr_rec2* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor,
                                 bsx_stats2* stats) {
     if (!h) return BSX_ERR_INVALID;
+    if (h->wide) return fail(h, BSX_ERR_UNSUPPORTED, "networks of the wide-state family (more than BSX_MAX_NODES nodes, or BSX_WIDE=1): use bsx_run_attract_wide");
     if (!table || !n_out) return fail(h, BSX_ERR_INVALID, "table / n_out is null");
     if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
     // flat index I = init_digits + variant * 2^n_any (batching.py:212-229)
@@ -1587,6 +1589,7 @@ extern "C" int bsx_run_attract_fgraph(bsx_handle h, const bsx_index* first, uint
                                       uint64_t max_len, bsx_attr_rec* table, uint32_t cap, uint32_t* n_out,
                                       uint64_t* n_no_attractor, bsx_stats* stats) {
     if (!h) return BSX_ERR_INVALID;
+    if (h->wide) return fail(h, BSX_ERR_UNSUPPORTED, "networks of the wide-state family (more than BSX_MAX_NODES nodes, or BSX_WIDE=1): use bsx_run_attract_wide");
     if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
     if (!table || !n_out) return fail(h, BSX_ERR_INVALID, "table / n_out is null");
     if (int rc = check_range(h, first, count)) return rc;

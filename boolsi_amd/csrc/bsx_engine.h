@@ -13,6 +13,8 @@
 
 namespace bsx {
 
+struct WideHost;        // bsx_wide_api.cpp
+
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
@@ -138,6 +140,9 @@ struct bsx_engine {
     bsx::DevBuf<uint32_t> d_fg_a, d_fg_b, d_fg_c, d_fg_warm;
     bsx::DevBuf<unsigned long long> d_fg_pair;
 
+    // wide-state family (bsx_wide_api.cpp): set when the network has more than BSX_MAX_NODES nodes or BSX_WIDE=1
+    bsx::WideHost* wide = nullptr;
+
     // RCCL communicator of this handle's rank (bsx_comm.cpp); librccl is loaded on first use
     void* comm = nullptr;       // ncclComm_t
     int comm_rank = 0, comm_world = 1;
@@ -152,6 +157,22 @@ struct bsx_engine {
             return BSX_ERR_HIP;                                                              \
         }                                                                                    \
     } while (0)
+
+namespace bsx {
+bool wide_forced();
+void wide_release(bsx_handle h);
+int wide_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* pred_offsets, const uint32_t* pred_idx,
+                     const uint32_t* tt_word_offsets, const uint64_t* tt_words);
+int wide_set_problem_space(bsx_handle h, const uint64_t* origin_state_words, const uint32_t* any_nodes, uint32_t n_any,
+                           const bsx_fixed* fixed, uint32_t n_fixed, const bsx_fixed_var* fixed_var, uint32_t n_fixed_var,
+                           const bsx_pert* sched, uint32_t n_sched, const bsx_pert_var* pert_var, uint32_t n_pert_var);
+int wide_run_simulate(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, uint64_t* trajectories,
+                      uint64_t* final_states, uint64_t* digests, bsx_stats* stats);
+int wide_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* offsets, const uint64_t* t_len, uint64_t n,
+                          uint64_t* out, const uint64_t* out_offsets, bsx_stats* stats);
+int wide_target_times(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
+                      const uint64_t* code_words, std::vector<uint32_t>& t_hit, bsx_stats* stats);
+}  // namespace bsx
 
 static inline int fail(bsx_handle h, int status, const std::string& msg) {
     if (h) h->error = msg;

@@ -1,0 +1,70 @@
+// Wide-state family (257 <= n <= BSX_MAX_NODES_WIDE, or any n with BSX_WIDE=1): kernel parameters shared by
+// bsx_wide.hip and bsx_wide_api.cpp.  See DESIGN.md "Wide networks".
+//
+// Bit-sliced like k_simulate_sliced: a group of 32 * L trajectories is a rows x L matrix of 32-bit words in LDS,
+// row i = node i, column c = trajectories 32c .. 32c + 31, bit b of a word = trajectory 32c + b.  The 256 threads
+// of a workgroup are (slice, column) pairs: column c = tid % L, slice s = tid / L owns the contiguous rows
+// [s * rows_ps, (s + 1) * rows_ps).  A step costs the same per trajectory update whatever n is; L shrinks with n
+// so that four such matrices fit the LDS.
+#pragma once
+#include <stdint.h>
+
+namespace bsx {
+
+constexpr uint32_t kWideThreads = 256;
+constexpr uint32_t kWideMaxW32 = 32;            // 32-bit words of a state (n <= 1024)
+constexpr uint32_t kWideNone = 0xFFFFFFFFu;
+constexpr uint32_t kWideDescWords = 8;          // per row: preds (u16 x 6) in words 0..2, table bits 3..4, fixed slot 5, K>6 index 6
+constexpr uint32_t kWideBuffers = 4;            // state matrices a workgroup holds in LDS
+// Internal step limit, in lock steps of a group (BSX_ERR_STEP_LIMIT beyond it).  A lock step costs microseconds, not
+// one lane's nanoseconds, so this is 2^24 rather than the per-lane kernels' 2^30: a chaotic network with max_t = inf
+// gives up after minutes.  (BSX_WIDE_STEP_LIMIT lowers it, for tests.)
+constexpr uint32_t kWideStepLimit = 1u << 24;
+
+enum WideMode : uint32_t { kWideSimulate = 0, kWideTarget = 1, kWideAttract = 2 };
+
+struct WideParams {
+    uint32_t mode;
+    uint32_t n_nodes, rows, L, lshift, rows_ps, w64, pad0;
+    const uint32_t* desc;       // [rows][8]
+    const uint32_t* wdesc;      // per node with more than 6 predecessors: k, first pred, first table word (u32 words); null: none
+    const uint32_t* wpreds;
+    const uint32_t* wtt;
+    // problem space (bsx_index first + offset, batching.py:212-229)
+    uint64_t first_digits[4];
+    uint64_t first_variant;
+    uint32_t origin[kWideMaxW32];   // origin state ('any' nodes cleared)
+    uint32_t tmask[kWideMaxW32];    // target substate (target mode)
+    uint32_t tcode[kWideMaxW32];
+    uint32_t n_any, n_fv, n_pv, n_sched, n_fslots, tp_origin;
+    const uint32_t* any_nodes;  // [n_any]
+    const uint32_t* fv;         // [n_fv][3] node, range, fixed slot
+    const uint32_t* pv;         // [n_pv][3] t, node, range
+    const uint32_t* sched;      // [n_sched][3] t, node, value, sorted by t
+    uint64_t count;
+    uint64_t max_t;
+    uint32_t cap_inf;           // max_t is BSX_T_INF
+    uint32_t step_limit;        // kWideStepLimit (or BSX_WIDE_STEP_LIMIT)
+    // simulate / trajectories
+    const uint64_t* offsets;    // nullable: problem q = first + offsets[q]
+    const uint64_t* t_len;      // nullable: per-problem length (else max_t)
+    const uint64_t* out_offsets;
+    uint64_t* traj;
+    uint64_t* final_states;
+    uint64_t* digests;
+    // target: first hit time per problem, kWideNone = none
+    uint32_t* t_hit;
+    // attract: per problem (found-and-kept, lambda, trajectory_l lo, hi) and the key
+    uint32_t* info;
+    uint64_t* keys;
+    uint64_t max_len;
+    uint32_t* x0;               // scratch: [gridDim.x][rows * L] s(T_p) of the group
+    unsigned long long* ctr;    // [0] reference steps, [1] executed trajectory updates, [2] step-limit hits
+};
+
+// LDS words of a workgroup for L columns (bsx_wide.hip lays them out in this order).
+inline uint32_t wide_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslots, uint32_t n_pv) {
+    return kWideBuffers * rows * L + 2 * (n_fslots + n_pv) * L + 2 * kWideThreads + 8 * L + 4 * 32 * L + 8;
+}
+
+}  // namespace bsx

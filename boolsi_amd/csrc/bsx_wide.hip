@@ -1,0 +1,545 @@
+// Wide-state kernel family: simulate / trajectories, target and attract for networks of up to 1024 nodes
+// (bsx_wide.h has the layout).  One workgroup steps a group of 32 * L trajectories in lock step; problems with
+// different perturbation times, fixed-node variations and perturbation variations share a group through
+// per-trajectory masks, so the mode of the group's control flow is uniform:
+//   * warm-up (attract): trajectory b is frozen (its column bit keeps its value) after its own T_p, so that the
+//     matrix ends at s(T_p) for every b; from there all trajectories are autonomous;
+//   * Brent's detector: power-of-two checkpoints at the same relative time for every bit, "back at the
+//     checkpoint" = no row differs in that bit (OR over rows of cur ^ saved, reduced over the slices);
+//   * mu: a second lock-step pass, y = s(T_p + lambda_b) (bit b frozen after lambda_b steps) against x = s(T_p);
+//   * key: the minimum state over one lap of the cycle, by a bit-sliced lexicographic compare from the highest
+//     row down (per-slice lt / eq masks, combined across slices from the top).
+#include <hip/hip_runtime.h>
+
+#include "bsx_device.h"
+#include "bsx_wide.h"
+
+namespace bsx {
+
+namespace {
+
+__device__ __forceinline__ uint32_t wbfi(uint32_t sel, uint32_t a, uint32_t b) { return (a & sel) | (b & ~sel); }
+
+__device__ __forceinline__ int wide_digit_state(uint32_t range, uint32_t digit) {     // batching.py:171-175; -1 = absent
+    if (range == 0) return digit ? 0 : -1;
+    if (range == 1) return digit ? 1 : -1;
+    if (range == 2) return digit ? 1 : 0;
+    return digit == 0 ? -1 : (digit == 1 ? 0 : 1);
+}
+
+struct WideCtx {
+    uint32_t L, c, slice, r0, r1, RL, tid;
+};
+
+// One synchronous update of rows [r0, r1) of column c: rules, fixed-node variations, freeze mask (bits not in
+// `act` keep their value).  Origin fixed nodes are constant rules in the descriptors (model.py:31-49).
+template <int K, bool KW>
+__device__ __forceinline__ void wide_step(const WideParams& P, const WideCtx& X, const uint32_t* cur, uint32_t* nxt,
+                                          const uint32_t* fmv, uint32_t act) {
+    const uint32_t L = X.L, c = X.c;
+    for (uint32_t r = X.r0; r < X.r1; ++r) {
+        const uint4 d0 = *reinterpret_cast<const uint4*>(P.desc + (size_t)r * kWideDescWords);
+        const uint4 d1 = *reinterpret_cast<const uint4*>(P.desc + (size_t)r * kWideDescWords + 4);
+        uint32_t v;
+        if (KW && d1.z != kWideNone) {
+            // more than 6 predecessors: per-trajectory table lookups (32 indices built bit by bit)
+            const uint32_t* wd = P.wdesc + 3 * d1.z;
+            const uint32_t k = wd[0], poff = wd[1], toff = wd[2];
+            uint32_t idx[32];
+#pragma unroll
+            for (int b = 0; b < 32; ++b) idx[b] = 0;
+            for (uint32_t j = 0; j < k; ++j) {
+                const uint32_t g = cur[P.wpreds[poff + j] * L + c];
+#pragma unroll
+                for (int b = 0; b < 32; ++b) idx[b] |= ((g >> b) & 1u) << j;
+            }
+            v = 0;
+#pragma unroll
+            for (int b = 0; b < 32; ++b) v |= ((P.wtt[toff + (idx[b] >> 5)] >> (idx[b] & 31u)) & 1u) << b;
+        } else {
+            const uint32_t pw[3] = {d0.x, d0.y, d0.z};
+            const uint64_t tbits = ((uint64_t)d1.x << 32) | d0.w;
+            uint32_t g[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) g[j] = cur[((pw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) * L + c];
+            uint32_t m[1 << (K - 1)];
+#pragma unroll
+            for (int i = 0; i < (1 << (K - 1)); ++i) {
+                const uint32_t hi = 0u - (uint32_t)((tbits >> (2 * i + 1)) & 1u);
+                const uint32_t lo = 0u - (uint32_t)((tbits >> (2 * i)) & 1u);
+                m[i] = wbfi(g[0], hi, lo);
+            }
+#pragma unroll
+            for (int j = 1; j < K; ++j)
+#pragma unroll
+                for (int i = 0; i < (1 << (K - 1 - j)); ++i) m[i] = wbfi(g[j], m[2 * i + 1], m[2 * i]);
+            v = m[0];
+        }
+        if (d1.y != kWideNone) v = (v & ~fmv[(2 * d1.y) * L + c]) | fmv[(2 * d1.y + 1) * L + c];
+        nxt[r * L + c] = wbfi(act, v, cur[r * L + c]);
+    }
+}
+
+// Perturbation override at time t (model.py:68-71) on the matrix just written: origin schedule, then the
+// variations in list order (which win over an origin entry of the same (t, node), batching.py:198-207).
+// Uniform: returns whether anything was written (then the caller's barrier is needed before the next read).
+__device__ __forceinline__ bool wide_perturb(const WideParams& P, const WideCtx& X, uint64_t t, uint32_t* buf,
+                                             const uint32_t* pmv, uint32_t& sched_at) {
+    bool any = false;
+    while (sched_at < P.n_sched && P.sched[3 * sched_at] < t) ++sched_at;
+    for (uint32_t q = sched_at; q < P.n_sched && P.sched[3 * q] == t; ++q) {
+        if (X.tid < X.L) buf[P.sched[3 * q + 1] * X.L + X.tid] = P.sched[3 * q + 2] ? 0xFFFFFFFFu : 0u;
+        any = true;
+    }
+    for (uint32_t j = 0; j < P.n_pv; ++j) {
+        if (P.pv[3 * j] != t) continue;
+        if (X.tid < X.L) {
+            uint32_t& w = buf[P.pv[3 * j + 1] * X.L + X.tid];
+            w = (w & ~pmv[(2 * j) * X.L + X.tid]) | pmv[(2 * j + 1) * X.L + X.tid];
+        }
+        any = true;
+    }
+    return any;
+}
+
+// Bits of trajectory k: the 64 nodes of 64-bit state word w.
+__device__ __forceinline__ uint64_t wide_gather64(const WideParams& P, const uint32_t* buf, uint32_t L, uint32_t k, uint32_t w) {
+    uint64_t word = 0;
+    const uint32_t col = k >> 5, bit = k & 31u;
+    for (uint32_t i = 0; i < 64; ++i) {
+        const uint32_t node = w * 64 + i;
+        if (node >= P.n_nodes) break;
+        word |= (uint64_t)((buf[node * L + col] >> bit) & 1u) << i;
+    }
+    return word;
+}
+
+}  // namespace
+
+// KW: the network has nodes with more than 6 predecessors (their path's 32 table indices cost registers)
+template <int K, bool KW>
+__global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
+    WideCtx X;
+    X.L = P.L;
+    X.tid = threadIdx.x;
+    X.c = X.tid & (P.L - 1);
+    X.slice = X.tid >> P.lshift;
+    X.r0 = X.slice * P.rows_ps;
+    X.r1 = X.r0 + P.rows_ps;
+    X.RL = P.rows * P.L;
+    const uint32_t L = P.L, c = X.c, RL = X.RL, G = 32 * L, tid = X.tid;
+    const uint32_t nslices = kWideThreads / L;
+    uint32_t* B[4] = {sm, sm + RL, sm + 2 * RL, sm + 3 * RL};
+    uint32_t* fmv = sm + 4 * RL;                    // [n_fslots][2][L]  fixed-node variations: mask, value
+    uint32_t* pmv = fmv + 2 * P.n_fslots * L;       // [n_pv][2][L]      perturbation variations: mask, value
+    uint32_t* red = pmv + 2 * P.n_pv * L;           // [2][256]          per-thread partials
+    uint32_t* col = red + 2 * kWideThreads;         // [8][L]            per-column masks
+    uint32_t* tpa = col + 8 * L;                    // [G] T_p
+    uint32_t* lam = tpa + G;                        // [G] lambda
+    uint32_t* mua = lam + G;                        // [G] mu
+    uint32_t* sta = mua + G;                        // [G] state of the trajectory's search (below)
+    uint32_t* misc = sta + G;                       // [8]
+    enum : uint32_t { ST_ACTIVE = 0, ST_CAND = 1, ST_FOUND = 2, ST_NONE = 3, ST_INVALID = 4 };
+    unsigned long long steps_ref = 0, steps_exec = 0, limit_hits = 0;
+
+    const uint64_t n_groups = (P.count + G - 1) / G;
+    for (uint64_t group = blockIdx.x; group < n_groups; group += gridDim.x) {
+        const uint64_t base = group * G;
+        const uint32_t n_valid = (uint32_t)((P.count - base) < G ? (P.count - base) : G);
+        // ---- s(0) = origin | 'any' digits; per-trajectory fixed-node / perturbation masks and T_p
+        for (uint32_t i = tid; i < RL; i += kWideThreads) {
+            const uint32_t r = i >> P.lshift;
+            B[0][i] = (r < P.n_nodes && ((P.origin[r >> 5] >> (r & 31u)) & 1u)) ? 0xFFFFFFFFu : 0u;
+        }
+        for (uint32_t i = tid; i < 2 * (P.n_fslots + P.n_pv) * L; i += kWideThreads) fmv[i] = 0;
+        if (tid < 8) misc[tid] = 0;
+        __syncthreads();
+        for (uint32_t k = tid; k < G; k += kWideThreads) {
+            uint32_t tp = P.tp_origin, st = ST_ACTIVE;
+            if (k >= n_valid) {
+                st = ST_INVALID;
+            } else {
+                uint64_t p = base + k;
+                if (P.offsets) p = P.offsets[p];
+                // digits = first_digits + p; what spills over bit n_any goes to the variant number
+                uint64_t d[5];
+                unsigned long long carry = p;
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long a = P.first_digits[w], sum = a + carry;
+                    carry = (sum < a) ? 1ull : 0ull;
+                    d[w] = sum;
+                }
+                d[4] = carry;
+                const uint32_t sw = P.n_any >> 6, sb = P.n_any & 63;
+                uint64_t lo = d[0], hi = d[1];      // words sw, sw + 1 (selects: the array stays in registers)
+#pragma unroll
+                for (int w = 1; w < 5; ++w) {
+                    lo = (sw == (uint32_t)w) ? d[w] : lo;
+                    hi = (sw + 1 == (uint32_t)w) ? d[w] : hi;
+                }
+                if (sw >= 4) hi = 0;
+                const uint64_t over = sb ? ((lo >> sb) | (hi << (64 - sb))) : lo;
+                uint64_t variant = P.first_variant + over;
+                const uint32_t bit = 1u << (k & 31u), cw = k >> 5;
+                uint64_t sh[4] = {d[0], d[1], d[2], d[3]};
+                for (uint32_t j = 0; j < P.n_any; ++j) {
+                    if (sh[0] & 1u) atomicOr(&B[0][P.any_nodes[j] * L + cw], bit);
+                    sh[0] = (sh[0] >> 1) | (sh[1] << 63);
+                    sh[1] = (sh[1] >> 1) | (sh[2] << 63);
+                    sh[2] = (sh[2] >> 1) | (sh[3] << 63);
+                    sh[3] >>= 1;
+                }
+                for (uint32_t j = 0; j < P.n_fv; ++j) {
+                    const uint32_t range = P.fv[3 * j + 1], slot = P.fv[3 * j + 2];
+                    uint32_t digit;
+                    if (range == 3) { digit = (uint32_t)(variant % 3); variant /= 3; }
+                    else { digit = (uint32_t)(variant & 1); variant >>= 1; }
+                    const int s = wide_digit_state(range, digit);
+                    if (s < 0) continue;
+                    atomicOr(&fmv[(2 * slot) * L + cw], bit);
+                    if (s) atomicOr(&fmv[(2 * slot + 1) * L + cw], bit);
+                    else atomicAnd(&fmv[(2 * slot + 1) * L + cw], ~bit);
+                }
+                for (uint32_t j = 0; j < P.n_pv; ++j) {
+                    const uint32_t t = P.pv[3 * j], range = P.pv[3 * j + 2];
+                    uint32_t digit;
+                    if (range == 3) { digit = (uint32_t)(variant % 3); variant /= 3; }
+                    else { digit = (uint32_t)(variant & 1); variant >>= 1; }
+                    const int s = wide_digit_state(range, digit);
+                    if (s < 0) continue;
+                    atomicOr(&pmv[(2 * j) * L + cw], bit);
+                    if (s) atomicOr(&pmv[(2 * j + 1) * L + cw], bit);
+                    if (t > tp) tp = t;                             // model.py:125
+                }
+                atomicMax(&misc[0], tp);
+            }
+            tpa[k] = tp; sta[k] = st; lam[k] = 0; mua[k] = 0;
+        }
+        __syncthreads();
+        const uint32_t tp_max = misc[0];
+        uint32_t sched_at = 0;
+        uint32_t* cur = B[0];
+        uint32_t* nxt = B[1];
+        uint64_t group_steps = 0;
+
+        if (P.mode == kWideSimulate) {
+            // ---- s(0 .. T): trajectories as they pass, digest accumulators X / Y per row in B[2] / B[3]
+            uint64_t T = P.max_t;
+            if (P.t_len) {
+                if (tid == 0) misc[1] = 0;
+                __syncthreads();
+                for (uint32_t k = tid; k < n_valid; k += kWideThreads) atomicMax(&misc[1], (uint32_t)P.t_len[base + k]);
+                __syncthreads();
+                T = misc[1];
+            }
+            if (P.digests)
+                for (uint32_t i = tid; i < 2 * RL; i += kWideThreads) B[2][i] = 0;
+            __syncthreads();
+            for (uint64_t t = 0;; ++t) {
+                if (P.traj) {
+                    for (uint32_t i = tid; i < n_valid * P.w64; i += kWideThreads) {
+                        const uint32_t k = i / P.w64, w = i % P.w64;
+                        const uint64_t q = base + k;
+                        const uint64_t tl = P.t_len ? P.t_len[q] : P.max_t;
+                        if (t > tl) continue;
+                        const uint64_t at = P.out_offsets ? P.out_offsets[q] : q * (P.max_t + 1) * P.w64;
+                        P.traj[at + t * P.w64 + w] = wide_gather64(P, cur, L, k, w);
+                    }
+                }
+                if (P.digests) {
+                    const uint32_t ym = 0u - ((((uint32_t)t) * 0x9E3779B1u) >> 31);
+                    for (uint32_t r = X.r0; r < X.r1; ++r) {
+                        const uint32_t v = cur[r * L + c];
+                        B[2][r * L + c] ^= v;
+                        B[3][r * L + c] ^= v & ym;
+                    }
+                }
+                if (t == T) break;
+                wide_step<K, KW>(P, X, cur, nxt, fmv, 0xFFFFFFFFu);
+                __syncthreads();
+                if (wide_perturb(P, X, t + 1, nxt, pmv, sched_at)) __syncthreads();
+                uint32_t* s = cur; cur = nxt; nxt = s;
+                ++group_steps;
+            }
+            __syncthreads();
+            for (uint32_t k = tid; k < n_valid; k += kWideThreads) {
+                const uint64_t q = base + k;
+                if (P.digests) {
+                    uint64_t dg = kDigestSeed;
+                    for (uint32_t w = 0; w < P.w64; ++w) dg = (dg ^ wide_gather64(P, B[2], L, k, w)) * kDigestPrime;
+                    for (uint32_t w = 0; w < P.w64; ++w) dg = (dg ^ wide_gather64(P, B[3], L, k, w)) * kDigestPrime;
+                    for (uint32_t w = 0; w < P.w64; ++w) dg = (dg ^ wide_gather64(P, cur, L, k, w)) * kDigestPrime;
+                    P.digests[q] = dg;
+                }
+                if (P.final_states)
+                    for (uint32_t w = 0; w < P.w64; ++w) P.final_states[q * P.w64 + w] = wide_gather64(P, cur, L, k, w);
+            }
+            if (tid == 0) {
+                uint64_t ref = 0;
+                for (uint32_t k = 0; k < n_valid; ++k) ref += P.t_len ? P.t_len[base + k] : P.max_t;
+                steps_ref += ref;
+            }
+        } else if (P.mode == kWideTarget) {
+            // ---- first t >= T_p with s(t) & mask == code (target.py:109-133); a trajectory whose cycle has closed
+            //      (Brent from T_max = max T_p of the group, when every trajectory is autonomous) has shown all its
+            //      states and ends without a hit
+            uint32_t* T = B[2];
+            uint64_t t = 0, power = 1, lamc = 0;
+            // (as bsx_target.hip: a max_t at or beyond the step limit is the limit, and reaching it is BSX_ERR_STEP_LIMIT)
+            const uint64_t t_cap = (P.cap_inf || P.max_t >= P.step_limit) ? P.step_limit : P.max_t;
+            for (;;) {
+                uint32_t mism = 0, diff = 0;
+                for (uint32_t r = X.r0; r < X.r1; ++r) {
+                    const uint32_t v = cur[r * L + c];
+                    if (r < P.n_nodes && ((P.tmask[r >> 5] >> (r & 31u)) & 1u))
+                        mism |= v ^ (((P.tcode[r >> 5] >> (r & 31u)) & 1u) ? 0xFFFFFFFFu : 0u);
+                    if (t > tp_max) {
+                        diff |= v ^ T[r * L + c];
+                        if (lamc == power) T[r * L + c] = v;
+                    } else if (t == tp_max) {
+                        T[r * L + c] = v;
+                    }
+                }
+                red[tid] = mism;
+                red[kWideThreads + tid] = diff;
+                __syncthreads();
+                bool left = false;
+                if (tid < L) {
+                    uint32_t m = 0, df = 0;
+                    for (uint32_t s = 0; s < nslices; ++s) { m |= red[s * L + tid]; df |= red[kWideThreads + s * L + tid]; }
+                    for (uint32_t b = 0; b < 32; ++b) {
+                        const uint32_t k = 32 * tid + b;
+                        if (sta[k] != ST_ACTIVE) continue;
+                        const uint64_t tp = tpa[k];
+                        bool done = false;
+                        if (t >= tp && !((m >> b) & 1u)) {
+                            P.t_hit[base + k] = (uint32_t)t; done = true;
+                            steps_ref += t;
+                        } else if (t > tp_max && !((df >> b) & 1u)) {
+                            done = true; steps_ref += t;             // cycle closed without a hit
+                        } else if (t >= tp && t >= t_cap) {
+                            done = true;
+                            if (t_cap == P.step_limit) ++limit_hits;            // unbounded (or beyond the limit)
+                            else steps_ref += t;
+                        }
+                        if (done) sta[k] = ST_NONE;
+                        else left = true;
+                    }
+                }
+                if (t > tp_max && lamc == power) { power <<= 1; lamc = 0; }
+                if (!__syncthreads_or(left)) break;
+                wide_step<K, KW>(P, X, cur, nxt, fmv, 0xFFFFFFFFu);
+                __syncthreads();
+                if (wide_perturb(P, X, t + 1, nxt, pmv, sched_at)) __syncthreads();
+                uint32_t* s = cur; cur = nxt; nxt = s;
+                ++t; ++group_steps;
+                if (t > tp_max) ++lamc;
+            }
+        } else {
+            // ---- attract.  Warm-up: bit b runs while t <= T_p(b), so the matrix ends at s(T_p) for every b
+            for (uint32_t t = 1; t <= tp_max; ++t) {
+                if (tid < L) {
+                    uint32_t act = 0;
+                    for (uint32_t b = 0; b < 32; ++b) act |= (t <= tpa[32 * tid + b] ? 1u : 0u) << b;
+                    col[tid] = act;
+                }
+                __syncthreads();
+                wide_step<K, KW>(P, X, cur, nxt, fmv, col[c]);
+                __syncthreads();
+                if (wide_perturb(P, X, t, nxt, pmv, sched_at)) __syncthreads();
+                uint32_t* s = cur; cur = nxt; nxt = s;
+                ++group_steps;
+            }
+            uint32_t* x0 = P.x0 + (size_t)blockIdx.x * RL;
+            for (uint32_t r = X.r0; r < X.r1; ++r) x0[r * L + c] = cur[r * L + c];
+            // caps: found iff T_p + mu + lambda <= max_t (S7); Brent closes the cycle within 3 (mu + lambda) + 2 steps
+            // (as bsx_attract.hip: max_t - T_p at or beyond a quarter of the step limit counts as unbounded, ~0, and
+            // a trajectory that runs into the step limit then makes the call fail with BSX_ERR_STEP_LIMIT)
+            auto cap_of = [&](uint32_t k) -> uint64_t {
+                if (P.cap_inf) return ~0ull;
+                if (P.max_t < tpa[k]) return ~0ull - 1;                        // max_t < T_p: never found
+                return P.max_t - tpa[k] >= P.step_limit / 4 ? ~0ull : P.max_t - tpa[k];
+            };
+            if (tid < L) {
+                for (uint32_t b = 0; b < 32; ++b) {
+                    const uint32_t k = 32 * tid + b;
+                    if (sta[k] == ST_ACTIVE && !P.cap_inf && P.max_t < tpa[k]) sta[k] = ST_NONE;
+                }
+            }
+            // ---- Brent's detector in lock step; the tortoise lives in B[2]
+            {
+                uint32_t* T = B[2];
+                for (uint32_t r = X.r0; r < X.r1; ++r) T[r * L + c] = cur[r * L + c];
+                uint64_t tau = 0, power = 1, lamc = 0;
+                for (;;) {
+                    bool left = false;
+                    if (tid < L)
+                        for (uint32_t b = 0; b < 32; ++b) left = left || sta[32 * tid + b] == ST_ACTIVE;
+                    if (!__syncthreads_or(left)) break;
+                    wide_step<K, KW>(P, X, cur, nxt, fmv, 0xFFFFFFFFu);
+                    ++tau; ++lamc; ++group_steps;
+                    const bool tele = lamc == power;
+                    uint32_t diff = 0;
+                    for (uint32_t r = X.r0; r < X.r1; ++r) {          // (own rows only: no barrier between write and read)
+                        const uint32_t v = nxt[r * L + c];
+                        diff |= v ^ T[r * L + c];
+                        if (tele) T[r * L + c] = v;
+                    }
+                    red[tid] = diff;
+                    __syncthreads();
+                    if (tid < L) {
+                        uint32_t df = 0;
+                        for (uint32_t s = 0; s < nslices; ++s) df |= red[s * L + tid];
+                        for (uint32_t b = 0; b < 32; ++b) {
+                            const uint32_t k = 32 * tid + b;
+                            if (sta[k] != ST_ACTIVE) continue;
+                            const uint64_t cap = cap_of(k);
+                            if (!((df >> b) & 1u)) {
+                                lam[k] = (uint32_t)lamc;
+                                sta[k] = (uint64_t)lamc > cap ? ST_NONE : ST_CAND;
+                                if (sta[k] == ST_NONE) steps_ref += P.max_t;
+                            } else if (cap == ~0ull ? tau >= P.step_limit : tau >= 3 * cap + 2) {
+                                sta[k] = ST_NONE;
+                                if (cap == ~0ull) ++limit_hits;
+                                else steps_ref += P.max_t;
+                            }
+                        }
+                    }
+                    if (tele) { power <<= 1; lamc = 0; }
+                    uint32_t* s = cur; cur = nxt; nxt = s;
+                }
+            }
+            // ---- mu: y = s(T_p + lambda) (bit b frozen after lambda_b steps) in B[0] / B[1], x = s(T_p) in B[2] / B[3]
+            uint32_t lam_max = 0;
+            if (tid == 0) misc[2] = 0;
+            __syncthreads();
+            if (tid < L)
+                for (uint32_t b = 0; b < 32; ++b)
+                    if (sta[32 * tid + b] == ST_CAND) atomicMax(&misc[2], lam[32 * tid + b]);
+            __syncthreads();
+            lam_max = misc[2];
+            if (lam_max) {
+                uint32_t* ya = B[0]; uint32_t* yb = B[1];
+                uint32_t* xa = B[2]; uint32_t* xb = B[3];
+                for (uint32_t r = X.r0; r < X.r1; ++r) { ya[r * L + c] = x0[r * L + c]; xa[r * L + c] = x0[r * L + c]; }
+                for (uint32_t m = 0; m < lam_max; ++m) {
+                    if (tid < L) {
+                        uint32_t act = 0;
+                        for (uint32_t b = 0; b < 32; ++b) act |= (m < lam[32 * tid + b] ? 1u : 0u) << b;
+                        col[tid] = act;
+                    }
+                    __syncthreads();
+                    wide_step<K, KW>(P, X, ya, yb, fmv, col[c]);
+                    __syncthreads();
+                    uint32_t* s = ya; ya = yb; yb = s;
+                    ++group_steps;
+                }
+                for (uint64_t m = 0;; ++m) {
+                    uint32_t diff = 0;
+                    for (uint32_t r = X.r0; r < X.r1; ++r) diff |= ya[r * L + c] ^ xa[r * L + c];
+                    red[tid] = diff;
+                    __syncthreads();
+                    bool left = false;
+                    if (tid < L) {
+                        uint32_t df = 0;
+                        for (uint32_t s = 0; s < nslices; ++s) df |= red[s * L + tid];
+                        for (uint32_t b = 0; b < 32; ++b) {
+                            const uint32_t k = 32 * tid + b;
+                            if (sta[k] != ST_CAND) continue;
+                            const uint64_t cap = cap_of(k);
+                            if (!((df >> b) & 1u)) {
+                                mua[k] = (uint32_t)m;
+                                sta[k] = ST_FOUND;
+                                steps_ref += (uint64_t)tpa[k] + m + lam[k];
+                            } else if (m + 1 + lam[k] > cap) {
+                                sta[k] = ST_NONE;
+                                steps_ref += P.max_t;
+                            } else {
+                                left = true;
+                            }
+                        }
+                    }
+                    if (!__syncthreads_or(left)) break;
+                    wide_step<K, KW>(P, X, ya, yb, fmv, 0xFFFFFFFFu);
+                    wide_step<K, KW>(P, X, xa, xb, fmv, 0xFFFFFFFFu);
+                    __syncthreads();
+                    uint32_t* s = ya; ya = yb; yb = s;
+                    s = xa; xa = xb; xb = s;
+                    group_steps += 2;
+                }
+                // ---- key: minimum over a lap of lam_max steps from y (on the cycle of every found bit), min in xa
+                cur = ya; nxt = yb;
+                uint32_t* mn = xa;
+                for (uint32_t r = X.r0; r < X.r1; ++r) mn[r * L + c] = cur[r * L + c];
+                for (uint32_t m = 1; m < lam_max; ++m) {
+                    wide_step<K, KW>(P, X, cur, nxt, fmv, 0xFFFFFFFFu);
+                    __syncthreads();
+                    uint32_t* s = cur; cur = nxt; nxt = s;
+                    ++group_steps;
+                    uint32_t lt = 0, eq = 0xFFFFFFFFu;
+                    for (uint32_t r = X.r1; r-- > X.r0;) {
+                        const uint32_t v = cur[r * L + c], w = mn[r * L + c];
+                        lt |= eq & ~v & w;
+                        eq &= ~(v ^ w);
+                    }
+                    red[tid] = lt;
+                    red[kWideThreads + tid] = eq;
+                    __syncthreads();
+                    if (tid < L) {
+                        uint32_t LT = 0, EQ = 0xFFFFFFFFu;
+                        for (uint32_t s2 = nslices; s2-- > 0;) {
+                            LT |= EQ & red[s2 * L + tid];
+                            EQ &= red[kWideThreads + s2 * L + tid];
+                        }
+                        col[L + tid] = LT;
+                    }
+                    __syncthreads();
+                    const uint32_t sel = col[L + c];
+                    for (uint32_t r = X.r0; r < X.r1; ++r) mn[r * L + c] = wbfi(sel, cur[r * L + c], mn[r * L + c]);
+                }
+                __syncthreads();
+                nxt = mn;       // key matrix for the records below
+            }
+            // ---- per-problem records
+            for (uint32_t k = tid; k < n_valid; k += kWideThreads) {
+                const uint64_t q = base + k;
+                const bool keep = sta[k] == ST_FOUND && (uint64_t)lam[k] <= P.max_len;      // attract.py:294
+                const uint64_t tl = (uint64_t)tpa[k] + mua[k];
+                P.info[4 * q + 0] = keep ? 1u : 0u;
+                P.info[4 * q + 1] = keep ? lam[k] : 0u;
+                P.info[4 * q + 2] = keep ? (uint32_t)tl : 0u;
+                P.info[4 * q + 3] = keep ? (uint32_t)(tl >> 32) : 0u;
+                for (uint32_t w = 0; w < P.w64; ++w) P.keys[q * P.w64 + w] = keep ? wide_gather64(P, nxt, L, k, w) : 0ull;
+            }
+        }
+        steps_exec += group_steps * n_valid;
+        __syncthreads();
+    }
+    if (steps_ref) atomicAdd(&P.ctr[0], steps_ref);
+    if (tid == 0 && steps_exec) atomicAdd(&P.ctr[1], steps_exec);
+    if (limit_hits) atomicAdd(&P.ctr[2], limit_hits);
+}
+
+template <int K>
+static hipError_t launch_wide_k(dim3 grid, size_t shmem, hipStream_t st, const WideParams& P) {
+    const void* fn = P.wdesc ? (const void*)k_wide<K, true> : (const void*)k_wide<K, false>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return e;
+    void* args[] = {const_cast<WideParams*>(&P)};
+    return hipLaunchKernel(fn, grid, dim3(kWideThreads), args, shmem, st);
+}
+
+hipError_t launch_wide(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& P) {
+    switch (k) {
+        case 1: return launch_wide_k<1>(grid, shmem, st, P);
+        case 2: return launch_wide_k<2>(grid, shmem, st, P);
+        case 3: return launch_wide_k<3>(grid, shmem, st, P);
+        case 4: return launch_wide_k<4>(grid, shmem, st, P);
+        case 5: return launch_wide_k<5>(grid, shmem, st, P);
+        case 6: return launch_wide_k<6>(grid, shmem, st, P);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace bsx

@@ -1,0 +1,453 @@
+// Host side of the wide-state family (bsx_wide.hip): lowering of networks of up to BSX_MAX_NODES_WIDE nodes to
+// per-row descriptors, the run entry points of include/bsx.h for such networks, and bsx_run_attract_wide.
+// bsx_api.cpp hands a handle over here when its network has more than BSX_MAX_NODES nodes (or BSX_WIDE=1).
+#include <algorithm>
+#include <array>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <vector>
+
+#include "bsx_engine.h"
+#include "bsx_host.h"
+#include "bsx_wide.h"
+
+namespace bsx {
+
+hipError_t launch_wide(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& P);
+
+struct WideHost {
+    uint32_t n = 0, rows = 0, K = 1, w64 = 0;
+    std::vector<uint32_t> pred_offsets, pred_idx, tt_offsets;
+    std::vector<uint64_t> tt;
+    std::vector<uint32_t> wdesc, wpreds, wtt;
+    DevBuf<uint32_t> d_desc, d_wdesc, d_wpreds, d_wtt, d_any, d_fv, d_pv, d_sched, d_x0;
+    DevBuf<unsigned long long> d_ctr;
+    // problem space
+    bool have_space = false;
+    uint32_t origin[kWideMaxW32] = {};
+    uint32_t n_any = 0, n_fv = 0, n_pv = 0, n_sched = 0, n_fslots = 0, tp_origin = 0;
+    uint32_t L = 0;
+    size_t shmem = 0;
+};
+
+bool wide_forced() {
+    const char* e = std::getenv("BSX_WIDE");
+    return e && e[0] == '1';
+}
+
+void wide_release(bsx_handle h) {
+    delete h->wide;
+    h->wide = nullptr;
+}
+
+int wide_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* pred_offsets, const uint32_t* pred_idx,
+                     const uint32_t* tt_word_offsets, const uint64_t* tt_words) {
+    if (n_nodes > BSX_MAX_NODES_WIDE) return fail(h, BSX_ERR_UNSUPPORTED, "more than BSX_MAX_NODES_WIDE nodes");
+    HIPCHK(h, hipSetDevice(h->device));
+    h->have_net = false;
+    h->have_space = false;
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        if (pred_offsets[i + 1] < pred_offsets[i]) return fail(h, BSX_ERR_INVALID, "pred_offsets not monotone");
+        const uint32_t k = pred_offsets[i + 1] - pred_offsets[i];
+        if (k > BSX_MAX_PREDECESSORS) return fail(h, BSX_ERR_UNSUPPORTED, "node with more than BSX_MAX_PREDECESSORS predecessors");
+        if (k && !pred_idx) return fail(h, BSX_ERR_INVALID, "pred_idx is null");
+        for (uint32_t j = pred_offsets[i]; j < pred_offsets[i + 1]; ++j) {
+            if (pred_idx[j] >= n_nodes) return fail(h, BSX_ERR_INVALID, "predecessor index out of range");
+            if (j > pred_offsets[i] && pred_idx[j] <= pred_idx[j - 1])
+                return fail(h, BSX_ERR_INVALID, "predecessors must be strictly ascending");
+        }
+        const uint32_t need_words = k <= 6 ? 1u : (1u << (k - 6));
+        if (tt_word_offsets[i + 1] - tt_word_offsets[i] != need_words)
+            return fail(h, BSX_ERR_INVALID, "truth table of a node must have ceil(2^k / 64) words");
+    }
+    if (!h->wide) h->wide = new WideHost();
+    WideHost& W = *h->wide;
+    W.n = n_nodes;
+    W.rows = (n_nodes + 63) & ~63u;
+    W.w64 = (n_nodes + 63) / 64;
+    W.pred_offsets.assign(pred_offsets, pred_offsets + n_nodes + 1);
+    W.pred_idx.assign(pred_idx, pred_idx + pred_offsets[n_nodes]);
+    W.tt_offsets.assign(tt_word_offsets, tt_word_offsets + n_nodes + 1);
+    W.tt.assign(tt_words, tt_words + tt_word_offsets[n_nodes]);
+    W.wdesc.clear(); W.wpreds.clear(); W.wtt.clear();
+    uint32_t K = 1;
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        const uint32_t k = pred_offsets[i + 1] - pred_offsets[i];
+        if (k <= 6) { K = std::max(K, k); continue; }
+        W.wdesc.push_back(k); W.wdesc.push_back((uint32_t)W.wpreds.size()); W.wdesc.push_back((uint32_t)W.wtt.size());
+        for (uint32_t j = pred_offsets[i]; j < pred_offsets[i + 1]; ++j) W.wpreds.push_back(pred_idx[j]);
+        for (uint32_t w = tt_word_offsets[i]; w < tt_word_offsets[i + 1]; ++w) {
+            W.wtt.push_back((uint32_t)tt_words[w]);
+            W.wtt.push_back((uint32_t)(tt_words[w] >> 32));
+        }
+    }
+    W.K = K;
+    HIPCHK(h, W.d_wdesc.upload(W.wdesc));
+    HIPCHK(h, W.d_wpreds.upload(W.wpreds));
+    HIPCHK(h, W.d_wtt.upload(W.wtt));
+    HIPCHK(h, W.d_ctr.alloc(4));
+    W.have_space = false;
+    h->n_nodes = n_nodes;
+    h->w64 = W.w64;
+    h->net = DevNet{};
+    h->net.n_nodes = n_nodes;
+    h->net.nw = (n_nodes + 31) / 32;
+    h->net.k_mux = K;
+    h->lut_mode = BSX_LUT_WIDE;
+    h->have_net = true;
+    return BSX_OK;
+}
+
+int wide_set_problem_space(bsx_handle h, const uint64_t* origin_state_words, const uint32_t* any_nodes, uint32_t n_any,
+                           const bsx_fixed* fixed, uint32_t n_fixed, const bsx_fixed_var* fixed_var, uint32_t n_fixed_var,
+                           const bsx_pert* sched, uint32_t n_sched, const bsx_pert_var* pert_var, uint32_t n_pert_var) {
+    WideHost& W = *h->wide;
+    const uint32_t n = W.n;
+    if (n_any > 64 * BSX_MAX_WORDS)
+        return fail(h, BSX_ERR_UNSUPPORTED, "more 'any' nodes than a bsx_index holds (64 * BSX_MAX_WORDS)");
+    HIPCHK(h, hipSetDevice(h->device));
+    h->have_space = false;
+    W.have_space = false;
+    std::memset(W.origin, 0, sizeof(W.origin));
+    for (uint32_t i = 0; i < n; ++i)
+        if ((origin_state_words[i >> 6] >> (i & 63)) & 1ull) W.origin[i >> 5] |= 1u << (i & 31);
+    std::vector<uint32_t> any(n_any);
+    for (uint32_t j = 0; j < n_any; ++j) {
+        if (any_nodes[j] >= n || (j && any_nodes[j] <= any_nodes[j - 1]))
+            return fail(h, BSX_ERR_INVALID, "'any' nodes must be ascending node indices");
+        any[j] = any_nodes[j];
+        W.origin[any[j] >> 5] &= ~(1u << (any[j] & 31));
+    }
+    std::vector<int> fixed_val(n, -1), slot_of(n, -1);
+    for (uint32_t j = 0; j < n_fixed; ++j) {
+        if (fixed[j].node >= n || fixed[j].value > 1) return fail(h, BSX_ERR_INVALID, "bad fixed node entry");
+        fixed_val[fixed[j].node] = (int)fixed[j].value;
+    }
+    std::vector<uint32_t> fv, pv;
+    uint32_t n_slots = 0;
+    for (uint32_t j = 0; j < n_fixed_var; ++j) {
+        const uint32_t node = fixed_var[j].node;
+        if (node >= n || fixed_var[j].range > 3) return fail(h, BSX_ERR_INVALID, "bad fixed-node variation");
+        if (slot_of[node] < 0) slot_of[node] = (int)n_slots++;
+        fv.push_back(node); fv.push_back(fixed_var[j].range); fv.push_back((uint32_t)slot_of[node]);
+    }
+    uint32_t tp_origin = 0, tp_max = 0;
+    std::vector<std::array<uint32_t, 3>> ordered;
+    for (uint32_t j = 0; j < n_sched; ++j) {
+        if (sched[j].node >= n || sched[j].value > 1 || sched[j].t == 0) return fail(h, BSX_ERR_INVALID, "bad perturbation entry");
+        tp_origin = std::max(tp_origin, sched[j].t);
+        ordered.push_back({sched[j].t, sched[j].node, sched[j].value});
+    }
+    std::stable_sort(ordered.begin(), ordered.end(), [](const auto& a, const auto& b) { return a[0] < b[0]; });
+    std::vector<uint32_t> sch;
+    for (const auto& e : ordered) { sch.push_back(e[0]); sch.push_back(e[1]); sch.push_back(e[2]); }
+    tp_max = tp_origin;
+    for (uint32_t j = 0; j < n_pert_var; ++j) {
+        if (pert_var[j].node >= n || pert_var[j].range > 3 || pert_var[j].t == 0) return fail(h, BSX_ERR_INVALID, "bad perturbation variation");
+        pv.push_back(pert_var[j].t); pv.push_back(pert_var[j].node); pv.push_back(pert_var[j].range);
+        tp_max = std::max(tp_max, pert_var[j].t);
+    }
+    // row descriptors: K-input mux (tables replicated over unused inputs; origin fixed nodes are constant rules),
+    // fixed-variation slot, index of the per-trajectory path for nodes with more than 6 predecessors
+    std::vector<uint32_t> desc((size_t)W.rows * kWideDescWords, 0);
+    uint32_t wide_at = 0;
+    for (uint32_t i = 0; i < W.rows; ++i) {
+        uint32_t* d = &desc[(size_t)i * kWideDescWords];
+        d[5] = kWideNone;
+        d[6] = kWideNone;
+        if (i >= n) continue;                   // padding rows: constant 0
+        d[5] = slot_of[i] >= 0 ? (uint32_t)slot_of[i] : kWideNone;
+        const uint32_t k = W.pred_offsets[i + 1] - W.pred_offsets[i];
+        if (k > 6) {
+            const uint32_t at = wide_at++;
+            if (fixed_val[i] < 0) { d[6] = at; continue; }
+        }
+        uint64_t bits = 0;
+        if (fixed_val[i] >= 0) {
+            bits = fixed_val[i] ? ~0ull : 0ull;
+        } else {
+            const uint64_t t = W.tt[W.tt_offsets[i]];
+            for (uint32_t idx = 0; idx < 64; ++idx)
+                if ((t >> (idx & ((1u << k) - 1))) & 1ull) bits |= 1ull << idx;
+            for (uint32_t j = 0; j < k; ++j) {
+                const uint32_t p = W.pred_idx[W.pred_offsets[i] + j];
+                d[j >> 1] |= p << (16 * (j & 1));
+            }
+        }
+        d[3] = (uint32_t)bits;
+        d[4] = (uint32_t)(bits >> 32);
+    }
+    HIPCHK(h, W.d_desc.upload(desc));
+    HIPCHK(h, W.d_any.upload(any));
+    HIPCHK(h, W.d_fv.upload(fv));
+    HIPCHK(h, W.d_pv.upload(pv));
+    HIPCHK(h, W.d_sched.upload(sch));
+    W.n_any = n_any; W.n_fv = n_fixed_var; W.n_pv = n_pert_var; W.n_sched = (uint32_t)ordered.size();
+    W.n_fslots = n_slots; W.tp_origin = tp_origin;
+    // columns per group: the largest power of two <= 64 whose four matrices and tables fit the LDS
+    W.L = 0;
+    for (uint32_t L = 64; L >= 4; L >>= 1) {
+        const size_t bytes = (size_t)wide_lds_words(W.rows, L, W.n_fslots, W.n_pv) * 4;
+        if (bytes <= 159 * 1024) { W.L = L; W.shmem = bytes; break; }
+    }
+    if (!W.L) return fail(h, BSX_ERR_UNSUPPORTED, "wide network: state matrices do not fit the LDS");
+    // the fields of the handle that the range checks of bsx_host.h read
+    h->sp = DevSpace{};
+    h->sp.n_any = n_any;
+    {
+        unsigned __int128 v = 1;
+        auto times = [&](uint32_t range) { if (v <= UINT64_MAX) v *= (range == BSX_RANGE_MAYBE_TRUE_OR_FALSE ? 3u : 2u); };
+        for (uint32_t j = 0; j < n_fixed_var; ++j) times(fixed_var[j].range);
+        for (uint32_t j = 0; j < n_pert_var; ++j) times(pert_var[j].range);
+        h->variant_count_saturated = v > UINT64_MAX;
+        h->variant_count = h->variant_count_saturated ? UINT64_MAX : (uint64_t)v;
+    }
+    h->tp_max = tp_max;
+    W.have_space = true;
+    h->have_space = true;
+    return BSX_OK;
+}
+
+// One launch over [first, first + count) (count problems, or the listed offsets); fills the caller's
+// parameter fields for the mode's sinks before this is called.
+static int wide_launch(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t,
+                       unsigned long long (&ctr)[4], float& ms) {
+    WideHost& W = *h->wide;
+    P.n_nodes = W.n; P.rows = W.rows; P.L = W.L;
+    P.lshift = (uint32_t)__builtin_ctz(W.L);
+    P.rows_ps = W.rows / (kWideThreads / W.L);
+    P.w64 = W.w64;
+    P.desc = W.d_desc.p; P.wdesc = W.d_wdesc.p; P.wpreds = W.d_wpreds.p; P.wtt = W.d_wtt.p;
+    for (int w = 0; w < 4; ++w) P.first_digits[w] = first->init_digits[w];
+    P.first_variant = first->variant;
+    std::memcpy(P.origin, W.origin, sizeof(P.origin));
+    P.n_any = W.n_any; P.n_fv = W.n_fv; P.n_pv = W.n_pv; P.n_sched = W.n_sched; P.n_fslots = W.n_fslots;
+    P.tp_origin = W.tp_origin;
+    P.any_nodes = W.d_any.p; P.fv = W.d_fv.p; P.pv = W.d_pv.p; P.sched = W.d_sched.p;
+    P.count = count;
+    P.max_t = max_t;
+    P.cap_inf = max_t == BSX_T_INF ? 1u : 0u;
+    P.step_limit = kWideStepLimit;
+    if (const char* e = std::getenv("BSX_WIDE_STEP_LIMIT")) P.step_limit = std::max(16u, std::min(kWideStepLimit, (uint32_t)std::atoi(e)));
+    if (W.wdesc.empty()) P.wdesc = nullptr;
+    P.ctr = W.d_ctr.p;
+    const uint32_t G = 32 * W.L;
+    const uint64_t groups = (count + G - 1) / G;
+    const uint32_t per_cu = std::max<uint32_t>(1, (uint32_t)((160 * 1024) / W.shmem));
+    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>(groups, (uint64_t)h->prop.multiProcessorCount * per_cu));
+    if (P.mode == kWideAttract) {
+        HIPCHK(h, W.d_x0.reserve((size_t)blocks * W.rows * W.L));
+        P.x0 = W.d_x0.p;
+    }
+    HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    HIPCHK(h, launch_wide((int)W.K, dim3((uint32_t)blocks), W.shmem, h->stream, P));
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ctr, W.d_ctr.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    return BSX_OK;
+}
+
+static void put_stats(bsx_stats* stats, uint64_t problems, const unsigned long long (&ctr)[4], float ms, uint32_t launches,
+                      double t_begin) {
+    if (!stats) return;
+    stats->problems = problems;
+    stats->state_steps = ctr[0];
+    stats->executed_steps = ctr[1];
+    stats->kernel_ms = ms;
+    stats->kernel_launches = launches;
+    stats->total_ms = now_ms() - t_begin;
+}
+
+static int wide_sim(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* offsets,
+                    const uint64_t* t_len, const uint64_t* out_offsets, uint64_t traj_words, uint64_t* trajectories,
+                    uint64_t* final_states, uint64_t* digests, bsx_stats* stats) {
+    const double t_begin = now_ms();
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (count == 0) return BSX_OK;
+    if (max_t >= kStepLimit) return fail(h, BSX_ERR_UNSUPPORTED, "simulation length above the engine's step limit");
+    HIPCHK(h, hipSetDevice(h->device));
+    const uint32_t w64 = h->wide->w64;
+    DevBuf<uint64_t> d_traj, d_final, d_dig, d_off, d_tlen, d_ooff;
+    WideParams P{};
+    P.mode = kWideSimulate;
+    if (trajectories) { HIPCHK(h, d_traj.alloc(traj_words)); P.traj = d_traj.p; }
+    if (final_states) { HIPCHK(h, d_final.alloc(count * w64)); P.final_states = d_final.p; }
+    if (digests) { HIPCHK(h, d_dig.alloc(count)); P.digests = d_dig.p; }
+    if (offsets) {
+        HIPCHK(h, d_off.upload(std::vector<uint64_t>(offsets, offsets + count))); P.offsets = d_off.p;
+        HIPCHK(h, d_tlen.upload(std::vector<uint64_t>(t_len, t_len + count))); P.t_len = d_tlen.p;
+        HIPCHK(h, d_ooff.upload(std::vector<uint64_t>(out_offsets, out_offsets + count))); P.out_offsets = d_ooff.p;
+    }
+    unsigned long long ctr[4];
+    float ms = 0.f;
+    if (int rc = wide_launch(h, P, first, count, max_t, ctr, ms)) return rc;
+    if (trajectories) HIPCHK(h, hipMemcpy(trajectories, d_traj.p, traj_words * 8, hipMemcpyDeviceToHost));
+    if (final_states) HIPCHK(h, hipMemcpy(final_states, d_final.p, count * w64 * 8, hipMemcpyDeviceToHost));
+    if (digests) HIPCHK(h, hipMemcpy(digests, d_dig.p, count * 8, hipMemcpyDeviceToHost));
+    put_stats(stats, count, ctr, ms, 1, t_begin);
+    return BSX_OK;
+}
+
+int wide_run_simulate(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, uint64_t* trajectories,
+                      uint64_t* final_states, uint64_t* digests, bsx_stats* stats) {
+    return wide_sim(h, first, count, max_t, nullptr, nullptr, nullptr, trajectories ? count * (max_t + 1) * h->w64 : 0,
+                    trajectories, final_states, digests, stats);
+}
+
+int wide_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* offsets, const uint64_t* t_len, uint64_t n,
+                          uint64_t* out, const uint64_t* out_offsets, bsx_stats* stats) {
+    uint64_t words = 0, tmax = 0;
+    for (uint64_t q = 0; q < n; ++q) {
+        words = std::max(words, out_offsets[q] + (t_len[q] + 1) * h->w64);
+        tmax = std::max(tmax, t_len[q]);
+    }
+    return wide_sim(h, first, n, tmax, offsets, t_len, out_offsets, words, out, nullptr, nullptr, stats);
+}
+
+// target: first hit time per problem into t_hit (kWideNone = none)
+int wide_target_times(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
+                      const uint64_t* code_words, std::vector<uint32_t>& t_hit, bsx_stats* stats) {
+    const double t_begin = now_ms();
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    t_hit.assign(count, kWideNone);
+    if (count == 0) return BSX_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    WideParams P{};
+    P.mode = kWideTarget;
+    for (uint32_t i = 0; i < h->wide->n; ++i) {
+        if ((mask_words[i >> 6] >> (i & 63)) & 1ull) P.tmask[i >> 5] |= 1u << (i & 31);
+        if ((code_words[i >> 6] >> (i & 63)) & 1ull) P.tcode[i >> 5] |= 1u << (i & 31);
+    }
+    DevBuf<uint32_t> d_thit;
+    HIPCHK(h, d_thit.alloc(count));
+    HIPCHK(h, hipMemset(d_thit.p, 0xFF, count * 4));
+    P.t_hit = d_thit.p;
+    unsigned long long ctr[4];
+    float ms = 0.f;
+    if (int rc = wide_launch(h, P, first, count, max_t, ctr, ms)) return rc;
+    HIPCHK(h, hipMemcpy(t_hit.data(), d_thit.p, count * 4, hipMemcpyDeviceToHost));
+    put_stats(stats, count, ctr, ms, 1, t_begin);
+    if (ctr[2]) return fail(h, BSX_ERR_STEP_LIMIT, "a trajectory reached the internal step limit");
+    return BSX_OK;
+}
+
+}  // namespace bsx
+
+using namespace bsx;
+
+// ---- attract over wide records: per-problem results of the kernel, aggregated here by key
+extern "C" int bsx_run_attract_wide(bsx_handle h, bsx_u128 first_flat, bsx_u128 count_flat, uint64_t max_t, uint64_t max_len,
+                                    bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor,
+                                    bsx_stats2* stats) {
+    if (!h) return BSX_ERR_INVALID;
+    if (!table || !n_out) return fail(h, BSX_ERR_INVALID, "table / n_out is null");
+    if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
+    if (!h->wide) {
+        // networks of the <= 256-node family: bsx_run_attract2, keys zero-extended
+        std::vector<bsx_attr_rec2> t2(cap ? cap : 1);
+        const int rc = bsx_run_attract2(h, first_flat, count_flat, max_t, max_len, t2.data(), cap, n_out, n_no_attractor, stats);
+        if (rc != BSX_OK) return rc;
+        for (uint32_t i = 0; i < *n_out; ++i) {
+            bsx_attr_rec2w r{};
+            std::memcpy(r.key, t2[i].key, sizeof(t2[i].key));
+            r.length = t2[i].length; r.count = t2[i].count;
+            std::memcpy(r.sum_l, t2[i].sum_l, sizeof(r.sum_l));
+            std::memcpy(r.sum_l2, t2[i].sum_l2, sizeof(r.sum_l2));
+            table[i] = r;
+        }
+        return BSX_OK;
+    }
+    const double t_begin = now_ms();
+    *n_out = 0;
+    if (n_no_attractor) *n_no_attractor = bsx_u128{0, 0};
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (count_flat.hi) return fail(h, BSX_ERR_UNSUPPORTED, "wide networks: at most 2^64 - 1 problems per call");
+    const uint64_t count = count_flat.lo;
+    // flat index -> bsx_index: the low n_any bits are the initial-state digits, the rest is the variant
+    const uint32_t n_any = h->sp.n_any;
+    bsx_index first{};
+    const u128 flat = ((u128)first_flat.hi << 64) | first_flat.lo;
+    if (n_any >= 128) {
+        first.init_digits[0] = first_flat.lo; first.init_digits[1] = first_flat.hi;
+    } else {
+        const u128 digits = n_any ? (flat & ((((u128)1) << n_any) - 1)) : 0;
+        const u128 variant = flat >> n_any;
+        if (variant >> 64) return fail(h, BSX_ERR_INVALID, "first lies beyond the problem space");
+        first.init_digits[0] = (uint64_t)digits; first.init_digits[1] = (uint64_t)(digits >> 64);
+        first.variant = (uint64_t)variant;
+    }
+    if (int rc = check_range(h, &first, count)) return rc;
+    if (int rc = check_max_t(h, max_t)) return rc;
+    if (count == 0) return BSX_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    WideHost& W = *h->wide;
+    const uint64_t chunk = std::min<uint64_t>(count, 1ull << 18);
+    DevBuf<uint32_t> d_info;
+    DevBuf<uint64_t> d_keys;
+    HIPCHK(h, d_info.alloc(chunk * 4));
+    HIPCHK(h, d_keys.alloc(chunk * W.w64));
+    std::vector<uint32_t> info(chunk * 4);
+    std::vector<uint64_t> keys(chunk * W.w64);
+    struct Agg { uint64_t length = 0; u128 count = 0, sl = 0, sl2 = 0; };
+    std::map<std::array<uint64_t, BSX_MAX_STATE_WORDS>, Agg> agg;
+    u128 none = 0, ref_steps = 0;
+    uint64_t exec = 0;
+    double kms = 0;
+    uint32_t launches = 0;
+    bool limit = false;
+    for (uint64_t done = 0; done < count; done += chunk) {
+        const uint64_t m = std::min(chunk, count - done);
+        const bsx_index at = index_plus(first, done, n_any);
+        WideParams P{};
+        P.mode = kWideAttract;
+        P.info = d_info.p;
+        P.keys = d_keys.p;
+        P.max_len = max_len;
+        unsigned long long ctr[4];
+        float ms = 0.f;
+        if (int rc = wide_launch(h, P, &at, m, max_t, ctr, ms)) return rc;
+        HIPCHK(h, hipMemcpy(info.data(), d_info.p, m * 16, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(keys.data(), d_keys.p, m * W.w64 * 8, hipMemcpyDeviceToHost));
+        kms += ms; ++launches; exec += ctr[1]; ref_steps += ctr[0];
+        limit = limit || ctr[2];
+        for (uint64_t q = 0; q < m; ++q) {
+            if (!info[4 * q]) { ++none; continue; }
+            std::array<uint64_t, BSX_MAX_STATE_WORDS> k{};
+            for (uint32_t w = 0; w < W.w64; ++w) k[w] = keys[q * W.w64 + w];
+            Agg& a = agg[k];
+            const uint64_t l = (uint64_t)info[4 * q + 2] | ((uint64_t)info[4 * q + 3] << 32);
+            a.length = info[4 * q + 1];
+            a.count += 1; a.sl += l; a.sl2 += (u128)l * l;
+        }
+    }
+    if (limit) return fail(h, BSX_ERR_STEP_LIMIT, "a trajectory reached the internal step limit");
+    if (agg.size() > cap) return fail(h, BSX_ERR_TABLE_FULL, "more distinct attractors than the caller's capacity");
+    uint32_t i = 0;
+    for (const auto& e : agg) {
+        bsx_attr_rec2w r{};
+        std::memcpy(r.key, e.first.data(), sizeof(r.key));
+        r.length = e.second.length;
+        r.count = bsx_u128{(uint64_t)e.second.count, (uint64_t)(e.second.count >> 64)};
+        r.sum_l[0] = (uint64_t)e.second.sl; r.sum_l[1] = (uint64_t)(e.second.sl >> 64);
+        r.sum_l2[0] = (uint64_t)e.second.sl2; r.sum_l2[1] = (uint64_t)(e.second.sl2 >> 64);
+        table[i++] = r;
+    }
+    *n_out = i;
+    if (n_no_attractor) *n_no_attractor = bsx_u128{(uint64_t)none, (uint64_t)(none >> 64)};
+    if (stats) {
+        stats->problems = bsx_u128{count, 0};
+        stats->state_steps = bsx_u128{(uint64_t)ref_steps, (uint64_t)(ref_steps >> 64)};
+        stats->executed_steps = exec;
+        stats->kernel_ms = kms;
+        stats->dominant_ms = kms;
+        stats->dominant_executed_steps = exec;
+        stats->dominant_launches = launches;
+        stats->kernel_launches = launches;
+        stats->host_syncs = launches;
+        stats->total_ms = now_ms() - t_begin;
+    }
+    return BSX_OK;
+}

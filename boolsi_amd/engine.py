@@ -201,6 +201,22 @@ class Engine:
                                                ptr(table), cap, C.byref(n_out), C.byref(none), C.byref(st)))
         return AttractResult(table[:n_out.value].copy(), int(none), None, st.as_dict())
 
+    @property
+    def wide(self):
+        """The current network runs on the wide-state family (more than 256 nodes, or BSX_WIDE=1)."""
+        return self.network_info()['lut_mode'] == _lib.LUT_WIDE
+
+    def attract_wide(self, first, count, max_t=inf, max_len=inf, cap=65536):
+        """bsx_run_attract_wide: attract2 for networks of any supported size -> table of _lib.ATTR_REC2W."""
+        table = getattr(self, '_attr_table2w', None)
+        if table is None or len(table) < cap:
+            table = self._attr_table2w = np.zeros(cap, _lib.ATTR_REC2W)
+        n_out, none, st = C.c_uint32(), _lib.U128(), _lib.Stats2()
+        self._check(self._lib.bsx_run_attract_wide(self._h, _lib.U128.of(first), _lib.U128.of(count), _cap(max_t),
+                                                   _cap(max_len), ptr(table), cap, C.byref(n_out), C.byref(none),
+                                                   C.byref(st)))
+        return AttractResult(table[:n_out.value].copy(), int(none), None, st.as_dict())
+
     def target(self, first, count, max_t, mask_words, code_words, cap=None):
         cap = count if cap is None else cap
         hits = np.zeros(max(cap, 1), _lib.HIT)

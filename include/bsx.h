@@ -34,6 +34,12 @@ extern "C" {
 #define BSX_MAX_PREDECESSORS 24
 #define BSX_MAX_PERT_VARIATIONS 32
 #define BSX_T_INF            UINT64_MAX   /* "no cap" for max_t / max_len (the CLI's inf) */
+/* Networks of BSX_MAX_NODES < n <= BSX_MAX_NODES_WIDE nodes run on the wide-state family (DESIGN.md "Wide networks"):
+ * simulate, trajectories, target and target summary through the entry points below, attract through
+ * bsx_run_attract_wide only.  Their 'any' nodes must fit a bsx_index (at most 64 * BSX_MAX_WORDS). */
+#define BSX_MAX_NODES_WIDE   1024
+#define BSX_MAX_STATE_WORDS  16     /* uint64 words per state / key of the wide family */
+#define BSX_LUT_WIDE         3      /* bsx_network_info's lut_mode for a network lowered to the wide family */
 
 typedef enum {
     BSX_OK = 0,
@@ -202,6 +208,23 @@ int  bsx_run_attract_fgraph(bsx_handle h, const bsx_index* first, uint64_t count
                             uint64_t max_t, uint64_t max_len,
                             bsx_attr_rec* table, uint32_t cap, uint32_t* n_out,
                             uint64_t* n_no_attractor, bsx_stats* stats);
+
+/* attract for networks of any supported size (n <= BSX_MAX_NODES_WIDE): bsx_run_attract2's semantics and sums, keys of
+ * BSX_MAX_STATE_WORDS words.  For networks of the <= BSX_MAX_NODES family it returns what bsx_run_attract2 returns,
+ * keys zero-extended; bsx_run_attract / bsx_run_attract2 / bsx_run_attract_fgraph return BSX_ERR_UNSUPPORTED for
+ * wide networks.  count must fit 64 bits for wide networks. */
+typedef struct {
+    uint64_t key[BSX_MAX_STATE_WORDS];  /* min state code over the cycle */
+    uint64_t length;
+    bsx_u128 count;
+    uint64_t sum_l[3];
+    uint64_t sum_l2[4];
+} bsx_attr_rec2w;
+
+int  bsx_run_attract_wide(bsx_handle h, bsx_u128 first, bsx_u128 count,
+                          uint64_t max_t, uint64_t max_len,
+                          bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out,
+                          bsx_u128* n_no_attractor, bsx_stats2* stats);
 
 /* target (target.py:109-133): hits in ascending offset order into hits[0..*n_hits); mask/code are W words
  * (target node set / target substate code, input.py:580-661). */
