@@ -588,8 +588,10 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (count == 0) return BSX_OK;
     if (count > (1ull << 40)) return fail(h, BSX_ERR_INVALID, "at most 2^40 problems per call");
+    if (h->wide && !wide_host_reduce())         // counted and binned on the device (bsx_wide_reduce.hip)
+        return wide_target_summary(h, first, count, max_t, mask_words, code_words, hist, hist_bins, hits, cap, n_hits, n_listed, stats);
     if (h->wide) {
-        // per-problem first-hit times of the wide kernel, summarised here (chunks of 2^24 problems)
+        // BSX_WIDE_HOST_REDUCE=1: per-problem first-hit times of the wide kernel, summarised here (chunks of 2^24 problems)
         uint64_t total = 0, listed = 0;
         bsx_stats part{};
         if (stats) stats->problems = count;

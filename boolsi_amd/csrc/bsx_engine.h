@@ -160,6 +160,7 @@ struct bsx_engine {
 
 namespace bsx {
 bool wide_forced();
+bool wide_host_reduce();        // BSX_WIDE_HOST_REDUCE=1
 void wide_release(bsx_handle h);
 int wide_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* pred_offsets, const uint32_t* pred_idx,
                      const uint32_t* tt_word_offsets, const uint64_t* tt_words);
@@ -172,6 +173,9 @@ int wide_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* 
                           uint64_t* out, const uint64_t* out_offsets, bsx_stats* stats);
 int wide_target_times(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
                       const uint64_t* code_words, std::vector<uint32_t>& t_hit, bsx_stats* stats);
+int wide_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
+                        const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
+                        uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats);
 }  // namespace bsx
 
 static inline int fail(bsx_handle h, int status, const std::string& msg) {

@@ -62,6 +62,42 @@ struct WideParams {
     unsigned long long* ctr;    // [0] reference steps, [1] executed trajectory updates, [2] step-limit hits
 };
 
+// ---- device-side reduction of the kernel's per-problem records (bsx_wide_reduce.hip) ----
+// Attract: an open-addressing HBM table keyed by the whole w64-word key, linear probing.
+// Widths of the sums, for at most 2^64 - 1 problems per call (bsx_run_attract_wide refuses more) and
+// l = T_p + mu < 2^33:  count < 2^64 (1 word),  sum l < 2^97 (2 words),  sum l^2 < 2^130 (3 words).  The adds carry
+// across the words, so no field wraps and the result equals sums taken in unbounded integers.
+struct WideSlot {
+    uint32_t state;             // 0 empty, 1 key being written, 2 ready
+    uint32_t length;
+    unsigned long long count;
+    unsigned long long sum_l[2];
+    unsigned long long sum_l2[3];
+    unsigned long long key[kWideMaxW32 / 2];    // words past w64 stay 0
+};
+// A drained record: the layout of bsx_attr_rec2w (include/bsx.h).
+struct WideAttrRec {
+    uint64_t key[kWideMaxW32 / 2];
+    uint64_t length;
+    uint64_t count[2];
+    uint64_t sum_l[3];
+    uint64_t sum_l2[4];
+};
+// Header words in front of the drained records; one device-to-host copy brings header and records back.
+enum WideHdr : uint32_t {
+    kHdrNone = 0,               // records without an attractor
+    kHdrCursor = 1,             // ready slots seen by the drain (may exceed the capacity it packs)
+    kHdrOverflow = 2,           // bit 0: table full (a probe went round all slots), bit 1: a bounded spin gave up
+    kHdrHits = 3,               // target: problems that hit
+    kHdrCtr = 4,                // copy of WideParams::ctr[0..3]
+    kHdrWords = 8
+};
+constexpr uint32_t kWideReduceTile = 1024;      // records a workgroup of k_wide_reduce_attract combines in LDS
+constexpr uint32_t kWideReduceLdsSlots = 128;   // entries of that LDS table
+constexpr uint32_t kWideReduceMinSlots = 1024;  // smallest HBM table
+// Largest min(cap, count) reduced on the device: 2^21 slots of 184 bytes and 2^20 records of 208 bytes, 0.6 GB.
+constexpr uint64_t kWideReduceMaxCap = 1ull << 20;
+
 // LDS words of a workgroup for L columns (bsx_wide.hip lays them out in this order).
 inline uint32_t wide_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslots, uint32_t n_pv) {
     return kWideBuffers * rows * L + 2 * (n_fslots + n_pv) * L + 2 * kWideThreads + 8 * L + 4 * 32 * L + 8;

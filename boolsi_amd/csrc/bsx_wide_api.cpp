@@ -15,6 +15,15 @@
 namespace bsx {
 
 hipError_t launch_wide(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& P);
+hipError_t launch_wide_reduce_attract(const uint32_t* info, const uint64_t* keys, uint64_t m, uint32_t w64, WideSlot* table,
+                                      uint64_t slots, unsigned long long* hdr, hipStream_t st);
+hipError_t launch_wide_reduce_drain(const WideSlot* table, uint64_t slots, WideAttrRec* out, uint64_t cap, unsigned long long* hdr,
+                                    const unsigned long long* ctr, hipStream_t st);
+hipError_t launch_wide_reduce_target(const uint32_t* t_hit, uint64_t m, unsigned long long* hist, uint32_t bins,
+                                     unsigned long long* hdr, hipStream_t st);
+
+static_assert(sizeof(WideAttrRec) == sizeof(bsx_attr_rec2w), "drained records have the layout of bsx_attr_rec2w");
+static_assert(kWideMaxW32 / 2 == BSX_MAX_STATE_WORDS, "key words");
 
 struct WideHost {
     uint32_t n = 0, rows = 0, K = 1, w64 = 0;
@@ -23,6 +32,11 @@ struct WideHost {
     std::vector<uint32_t> wdesc, wpreds, wtt;
     DevBuf<uint32_t> d_desc, d_wdesc, d_wpreds, d_wtt, d_any, d_fv, d_pv, d_sched, d_x0;
     DevBuf<unsigned long long> d_ctr;
+    // device-side reduction (bsx_wide_reduce.hip): grow-only, reused from call to call
+    DevBuf<uint32_t> d_info, d_thit;
+    DevBuf<uint64_t> d_keys;
+    DevBuf<WideSlot> d_table;
+    DevBuf<unsigned long long> d_out, d_hist;   // d_out: kHdrWords header words, then the drained records
     // problem space
     bool have_space = false;
     uint32_t origin[kWideMaxW32] = {};
@@ -34,6 +48,21 @@ struct WideHost {
 bool wide_forced() {
     const char* e = std::getenv("BSX_WIDE");
     return e && e[0] == '1';
+}
+
+// BSX_WIDE_HOST_REDUCE=1: per-problem records and hit times are copied back and reduced on the host, chunk by chunk
+// (the path before bsx_wide_reduce.hip; kept for A/B runs and tests).
+bool wide_host_reduce() {
+    const char* e = std::getenv("BSX_WIDE_HOST_REDUCE");
+    return e && e[0] == '1';
+}
+
+// Problems per k_wide launch of a chunked run: BSX_WIDE_CHUNK clamped to [32 * L, 2^18], else `dflt`.
+static uint64_t wide_chunk(const WideHost& W, uint64_t dflt) {
+    const char* e = std::getenv("BSX_WIDE_CHUNK");
+    if (!e || !e[0]) return dflt;
+    const uint64_t v = std::strtoull(e, nullptr, 10);
+    return std::max<uint64_t>(32ull * W.L, std::min<uint64_t>(v, 1ull << 18));
 }
 
 void wide_release(bsx_handle h) {
@@ -209,10 +238,10 @@ int wide_set_problem_space(bsx_handle h, const uint64_t* origin_state_words, con
     return BSX_OK;
 }
 
-// One launch over [first, first + count) (count problems, or the listed offsets); fills the caller's
-// parameter fields for the mode's sinks before this is called.
-static int wide_launch(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t,
-                       unsigned long long (&ctr)[4], float& ms) {
+// Enqueues one k_wide launch over [first, first + count) (count problems, or the listed offsets) on the engine's
+// stream and returns without waiting; the caller fills the parameter fields of the mode's sinks before.  The kernel
+// ADDS to the counters in W.d_ctr: the caller zeroes them once, in front of its first launch.
+static int wide_enqueue(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t) {
     WideHost& W = *h->wide;
     P.n_nodes = W.n; P.rows = W.rows; P.L = W.L;
     P.lshift = (uint32_t)__builtin_ctz(W.L);
@@ -237,12 +266,21 @@ static int wide_launch(bsx_handle h, WideParams& P, const bsx_index* first, uint
     const uint32_t per_cu = std::max<uint32_t>(1, (uint32_t)((160 * 1024) / W.shmem));
     const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>(groups, (uint64_t)h->prop.multiProcessorCount * per_cu));
     if (P.mode == kWideAttract) {
+        // (grow-only: a chunked run's first launch is its largest, so the buffer never moves under a queued launch)
         HIPCHK(h, W.d_x0.reserve((size_t)blocks * W.rows * W.L));
         P.x0 = W.d_x0.p;
     }
+    HIPCHK(h, launch_wide((int)W.K, dim3((uint32_t)blocks), W.shmem, h->stream, P));
+    return BSX_OK;
+}
+
+// One launch, waited for: its counters and its device time.
+static int wide_launch(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t,
+                       unsigned long long (&ctr)[4], float& ms) {
+    WideHost& W = *h->wide;
     HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    HIPCHK(h, launch_wide((int)W.K, dim3((uint32_t)blocks), W.shmem, h->stream, P));
+    if (int rc = wide_enqueue(h, P, first, count, max_t)) return rc;
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     HIPCHK(h, hipMemcpyAsync(ctr, W.d_ctr.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -334,11 +372,173 @@ int wide_target_times(bsx_handle h, const bsx_index* first, uint64_t count, uint
     return BSX_OK;
 }
 
+// target summary on the device: k_wide_reduce_target counts and bins every chunk's t_hit right behind the k_wide
+// launch that wrote it.  A chunk's t_hit is copied to the host only while the caller's hit list has room; with
+// cap == 0, or once the list is full, the host waits once, at the end.  (The caller, bsx_run_target_summary, has
+// checked the arguments and zeroed the outputs; count > 0.)  Chunks are 2^24 problems, or BSX_WIDE_CHUNK.
+int wide_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
+                        const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
+                        uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats) {
+    const double t_begin = now_ms();
+    WideHost& W = *h->wide;
+    WideParams P0{};
+    P0.mode = kWideTarget;
+    for (uint32_t i = 0; i < W.n; ++i) {
+        if ((mask_words[i >> 6] >> (i & 63)) & 1ull) P0.tmask[i >> 5] |= 1u << (i & 31);
+        if ((code_words[i >> 6] >> (i & 63)) & 1ull) P0.tcode[i >> 5] |= 1u << (i & 31);
+    }
+    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(W, 1ull << 24));
+    const uint32_t bins_alloc = std::max<uint32_t>(hist_bins, 1);
+    HIPCHK(h, W.d_thit.reserve(chunk));
+    HIPCHK(h, W.d_hist.reserve(bins_alloc));
+    HIPCHK(h, W.d_out.reserve(kHdrWords));
+    HIPCHK(h, hipMemsetAsync(W.d_hist.p, 0, bins_alloc * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(W.d_out.p, 0, kHdrWords * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
+    uint64_t listed = 0;
+    uint32_t launches = 0;
+    double kms = 0;
+    bool timing = false;        // ev0 recorded, ev1 not yet: a run of launches the host has not waited for
+    std::vector<uint32_t> t_hit;
+    std::vector<bsx_hit> list;      // handed to the caller only when the call succeeds
+    auto wait = [&]() -> int {
+        float ms = 0.f;
+        HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        kms += ms;
+        timing = false;
+        return BSX_OK;
+    };
+    for (uint64_t done = 0; done < count; done += chunk) {
+        const uint64_t m = std::min(chunk, count - done);
+        const bsx_index at = index_plus(*first, done, h->sp.n_any);
+        HIPCHK(h, hipMemsetAsync(W.d_thit.p, 0xFF, m * 4, h->stream));
+        if (!timing) { HIPCHK(h, hipEventRecord(h->ev0, h->stream)); timing = true; }
+        WideParams P = P0;
+        P.t_hit = W.d_thit.p;
+        if (int rc = wide_enqueue(h, P, &at, m, max_t)) return rc;
+        HIPCHK(h, launch_wide_reduce_target(W.d_thit.p, m, W.d_hist.p, hist_bins, W.d_out.p, h->stream));
+        launches += 2;
+        if (listed < cap) {                     // the list still has room: this chunk's hit times, in index order
+            if (int rc = wait()) return rc;
+            t_hit.resize(m);
+            HIPCHK(h, hipMemcpy(t_hit.data(), W.d_thit.p, m * 4, hipMemcpyDeviceToHost));
+            for (uint64_t p = 0; p < m && listed < cap; ++p)
+                if (t_hit[p] != kWideNone) { list.push_back(bsx_hit{done + p, t_hit[p]}); ++listed; }
+        }
+    }
+    if (timing) if (int rc = wait()) return rc;
+    unsigned long long hdr[kHdrWords], ctr[4];
+    std::vector<unsigned long long> bins(bins_alloc);
+    HIPCHK(h, hipMemcpyAsync(hdr, W.d_out.p, sizeof(hdr), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ctr, W.d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(bins.data(), W.d_hist.p, bins_alloc * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (stats) {
+        stats->problems = count;
+        stats->state_steps = ctr[0];
+        stats->executed_steps = ctr[1];
+        stats->kernel_ms = kms;                 // HIP events around each run of launches the host waited for
+        stats->kernel_launches = launches;
+        stats->total_ms = now_ms() - t_begin;
+    }
+    if (ctr[2]) return fail(h, BSX_ERR_STEP_LIMIT, "a trajectory reached the internal step limit");
+    for (uint32_t b = 0; b < hist_bins; ++b) hist[b] = bins[b];
+    *n_hits = hdr[kHdrHits];
+    std::copy(list.begin(), list.end(), hits);
+    if (n_listed) *n_listed = listed;
+    return BSX_OK;
+}
+
 }  // namespace bsx
 
 using namespace bsx;
 
-// ---- attract over wide records: per-problem results of the kernel, aggregated here by key
+// ---- attract over wide records: the kernel's per-problem results, aggregated by key
+// Device path: k_wide and k_wide_reduce_attract are enqueued for every chunk back to back (one info / keys buffer:
+// the stream orders them), k_wide_reduce_drain packs the table, and the host waits once.  The first
+// kInlineRecs records come back with the header in that one copy; a table with more costs a second copy.
+static constexpr uint32_t kInlineRecs = 256;
+
+static int attract_wide_device(bsx_handle h, const bsx_index& first, uint64_t count, uint64_t chunk, uint64_t max_t,
+                               uint64_t max_len, bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out,
+                               bsx_u128* n_no_attractor, bsx_stats2* stats, double t_begin) {
+    WideHost& W = *h->wide;
+    const uint32_t n_any = h->sp.n_any;
+    // a range of `count` problems has at most `count` attractors: the device structures follow the smaller of the two,
+    // so a caller's very large cap ("no limit") costs nothing
+    const uint64_t dcap = std::min<uint64_t>(cap, count);
+    uint64_t slots = kWideReduceMinSlots;
+    while (slots < 2 * dcap) slots <<= 1;
+    constexpr size_t kRecWords = sizeof(WideAttrRec) / 8;
+    HIPCHK(h, W.d_info.reserve(chunk * 4));
+    HIPCHK(h, W.d_keys.reserve(chunk * W.w64));
+    HIPCHK(h, W.d_table.reserve(slots));
+    HIPCHK(h, W.d_out.reserve(kHdrWords + (size_t)std::max<uint64_t>(dcap, 1) * kRecWords));
+    unsigned long long* d_hdr = W.d_out.p;
+    WideAttrRec* d_recs = reinterpret_cast<WideAttrRec*>(W.d_out.p + kHdrWords);
+    HIPCHK(h, hipMemsetAsync(W.d_table.p, 0, slots * sizeof(WideSlot), h->stream));
+    HIPCHK(h, hipMemsetAsync(d_hdr, 0, kHdrWords * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    uint32_t wide_launches = 0;
+    for (uint64_t done = 0; done < count; done += chunk) {
+        const uint64_t m = std::min(chunk, count - done);
+        const bsx_index at = index_plus(first, done, n_any);
+        WideParams P{};
+        P.mode = kWideAttract;
+        P.info = W.d_info.p;
+        P.keys = W.d_keys.p;
+        P.max_len = max_len;
+        if (int rc = wide_enqueue(h, P, &at, m, max_t)) return rc;
+        HIPCHK(h, launch_wide_reduce_attract(W.d_info.p, W.d_keys.p, m, W.w64, W.d_table.p, slots, d_hdr, h->stream));
+        ++wide_launches;
+    }
+    HIPCHK(h, launch_wide_reduce_drain(W.d_table.p, slots, d_recs, dcap, d_hdr, W.d_ctr.p, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    const uint32_t inl = (uint32_t)std::min<uint64_t>(dcap, kInlineRecs);
+    std::vector<unsigned long long> back(kHdrWords + (size_t)inl * kRecWords);
+    HIPCHK(h, hipMemcpyAsync(back.data(), W.d_out.p, back.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    uint32_t syncs = 1;
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    const unsigned long long* hdr = back.data();
+    if (hdr[kHdrCtr + 2]) return fail(h, BSX_ERR_STEP_LIMIT, "a trajectory reached the internal step limit");
+    if (hdr[kHdrOverflow] & 2) return fail(h, BSX_ERR_HIP, "wide attract reduction: a table slot stayed half-written");
+    if ((hdr[kHdrOverflow] & 1) || hdr[kHdrCursor] > cap)
+        return fail(h, BSX_ERR_TABLE_FULL, "more distinct attractors than the caller's capacity");
+    const uint32_t n = (uint32_t)hdr[kHdrCursor];
+    std::vector<bsx_attr_rec2w> recs(n);
+    const uint32_t n_inl = std::min(n, inl);
+    if (n_inl) std::memcpy(recs.data(), back.data() + kHdrWords, (size_t)n_inl * sizeof(WideAttrRec));
+    if (n > n_inl) {
+        HIPCHK(h, hipMemcpy(recs.data() + n_inl, d_recs + n_inl, (size_t)(n - n_inl) * sizeof(WideAttrRec), hipMemcpyDeviceToHost));
+        ++syncs;
+    }
+    // the order of the host path's std::map over key arrays: lexicographic from word 0
+    std::sort(recs.begin(), recs.end(), [](const bsx_attr_rec2w& a, const bsx_attr_rec2w& b) {
+        return std::lexicographical_compare(a.key, a.key + BSX_MAX_STATE_WORDS, b.key, b.key + BSX_MAX_STATE_WORDS);
+    });
+    std::copy(recs.begin(), recs.end(), table);
+    *n_out = n;
+    if (n_no_attractor) *n_no_attractor = bsx_u128{hdr[kHdrNone], 0};
+    if (stats) {
+        stats->problems = bsx_u128{count, 0};
+        stats->state_steps = bsx_u128{hdr[kHdrCtr + 0], 0};
+        stats->executed_steps = hdr[kHdrCtr + 1];
+        stats->kernel_ms = ms;                  // HIP events around the whole chain of launches
+        stats->dominant_ms = ms;
+        stats->dominant_executed_steps = hdr[kHdrCtr + 1];
+        stats->dominant_launches = wide_launches;
+        stats->kernel_launches = 2 * wide_launches + 1;
+        stats->host_syncs = syncs;
+        stats->total_ms = now_ms() - t_begin;
+    }
+    return BSX_OK;
+}
+
 extern "C" int bsx_run_attract_wide(bsx_handle h, bsx_u128 first_flat, bsx_u128 count_flat, uint64_t max_t, uint64_t max_len,
                                     bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor,
                                     bsx_stats2* stats) {
@@ -384,7 +584,11 @@ extern "C" int bsx_run_attract_wide(bsx_handle h, bsx_u128 first_flat, bsx_u128 
     if (count == 0) return BSX_OK;
     HIPCHK(h, hipSetDevice(h->device));
     WideHost& W = *h->wide;
-    const uint64_t chunk = std::min<uint64_t>(count, 1ull << 18);
+    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(W, 1ull << 18));
+    // (more than kWideReduceMaxCap possible attractors: the device table would take gigabytes; such a call is reduced
+    // on the host, which allocates per attractor found)
+    if (!wide_host_reduce() && std::min<uint64_t>(cap, count) <= kWideReduceMaxCap) return attract_wide_device(h, first, count, chunk, max_t, max_len, table, cap, n_out, n_no_attractor, stats, t_begin);
+    // BSX_WIDE_HOST_REDUCE=1 (or a table beyond kWideReduceMaxCap): every chunk's records come back and are aggregated here by key
     DevBuf<uint32_t> d_info;
     DevBuf<uint64_t> d_keys;
     HIPCHK(h, d_info.alloc(chunk * 4));

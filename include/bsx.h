@@ -185,7 +185,9 @@ typedef struct {
     uint64_t dominant_executed_steps;  /* network updates those launches executed (the roofline's numerator) */
     uint32_t dominant_launches;
     uint32_t kernel_launches;
-    uint32_t host_syncs;           /* times the host waited for the device inside the call */
+    uint32_t host_syncs;           /* times the host waited for the device inside the call (bsx_run_attract_wide on a
+                                    * wide network: 1, or 2 for tables of more than 256 records, whatever the count;
+                                    * kernel_ms there is taken from events around the whole chain of launches) */
     uint32_t lower_launches;       /* launches of the cascades' lower levels that had classes to work on ... */
     double   lower_ms;             /* ... their device time (first workgroup in to last one out, the device's 100 MHz clock) */
     uint64_t lower_executed_steps; /* ... and the network updates they executed */
@@ -212,7 +214,10 @@ int  bsx_run_attract_fgraph(bsx_handle h, const bsx_index* first, uint64_t count
 /* attract for networks of any supported size (n <= BSX_MAX_NODES_WIDE): bsx_run_attract2's semantics and sums, keys of
  * BSX_MAX_STATE_WORDS words.  For networks of the <= BSX_MAX_NODES family it returns what bsx_run_attract2 returns,
  * keys zero-extended; bsx_run_attract / bsx_run_attract2 / bsx_run_attract_fgraph return BSX_ERR_UNSUPPORTED for
- * wide networks.  count must fit 64 bits for wide networks. */
+ * wide networks.  count must fit 64 bits for wide networks.  There the records are aggregated on the device
+ * (DESIGN.md "Wide networks"); the table comes back sorted by key words from key[0] up.  Device memory of the call
+ * follows min(cap, count): about 600 bytes per possible attractor, kept on the handle; beyond 2^20 possible attractors
+ * the records are aggregated on the host instead, as with BSX_WIDE_HOST_REDUCE=1. */
 typedef struct {
     uint64_t key[BSX_MAX_STATE_WORDS];  /* min state code over the cycle */
     uint64_t length;

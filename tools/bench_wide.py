@@ -1,9 +1,10 @@
 """
 Wide-state family (DESIGN.md §3 "Wide networks"): executed node updates per second, one JSON line per case.
-  simulate: fixed max_t, final states only;  attract: bsx_run_attract_wide over a sweep of 'any' initial states;
+  simulate: fixed max_t, final states only;  attract: bsx_run_attract_wide over a sweep of 'any' initial states that
+  spans several kernel launches, reduced on the device and, for comparison, on the host (BSX_WIDE_HOST_REDUCE=1);
   n = 128 forced through BSX_WIDE=1 next to the per-lane / k_simulate_sliced path the library picks by default.
 
-    python tools/bench_wide.py [--count N] [--max-t T]
+    python tools/bench_wide.py [--count N] [--max-t T] [--attract-count N] [--attract-max-t T]
 """
 import argparse
 import json
@@ -40,7 +41,7 @@ def main():
     # (enough groups of 32 L trajectories for every CU of a 256-CU part: L = 16 at n = 300 / 512, 8 at 1024)
     ap.add_argument('--count', type=int, default=1 << 18)
     ap.add_argument('--max-t', type=int, default=256)
-    ap.add_argument('--attract-count', type=int, default=1 << 17)
+    ap.add_argument('--attract-count', type=int, default=1 << 20)      # four launches of 2^18 problems
     ap.add_argument('--attract-max-t', type=int, default=512)
     a = ap.parse_args()
     with Engine(0) as eng:
@@ -53,13 +54,20 @@ def main():
                                   'lut_mode': info['lut_mode'], 'kernel_ms': st['kernel_ms'],
                                   'node_updates_per_s': st['executed_steps'] * net.n_nodes / (st['kernel_ms'] * 1e-3),
                                   'wall_s': wall}), flush=True)
-                r, wall = timed(lambda: eng.attract_wide(0, a.attract_count, a.attract_max_t))
-                st = r.stats
-                print(json.dumps({'case': 'attract', 'n': n, 'k': k, 'count': a.attract_count,
-                                  'max_t': a.attract_max_t, 'attractors': len(r.table), 'none': r.n_no_attractor,
-                                  'kernel_ms': st['kernel_ms'],
-                                  'node_updates_per_s': st['executed_steps'] * net.n_nodes / (st['kernel_ms'] * 1e-3),
-                                  'wall_s': wall}), flush=True)
+                for reduce in ('device', 'host'):
+                    if reduce == 'host':
+                        os.environ['BSX_WIDE_HOST_REDUCE'] = '1'
+                    else:
+                        os.environ.pop('BSX_WIDE_HOST_REDUCE', None)
+                    r, wall = timed(lambda: eng.attract_wide(0, a.attract_count, a.attract_max_t))
+                    st = r.stats
+                    print(json.dumps({'case': 'attract', 'reduce': reduce, 'n': n, 'k': k, 'count': a.attract_count,
+                                      'max_t': a.attract_max_t, 'attractors': len(r.table), 'none': r.n_no_attractor,
+                                      'kernel_ms': st['kernel_ms'], 'total_ms': st['total_ms'],
+                                      'host_syncs': st['host_syncs'], 'kernel_launches': st['kernel_launches'],
+                                      'node_updates_per_s': st['executed_steps'] * net.n_nodes / (st['kernel_ms'] * 1e-3),
+                                      'wall_s': wall}), flush=True)
+                os.environ.pop('BSX_WIDE_HOST_REDUCE', None)
         for forced in (False, True):
             for k in (2, 3):
                 if forced:

@@ -39,6 +39,9 @@ LAUNCHED = {
     'bsx::k_simulate_sliced64<4, 3, false>': 'config 5, final states only',
     'bsx::k_attract<2, 3, 1>': 'chaotic K = 3 networks (n = 64): every trajectory through the detector',
     'bsx::k_publish': 'cube cascade: counters to the host',
+    'bsx::k_wide_reduce_attract': 'wide networks: attract records of a chunk into the HBM table (behind every k_wide attract launch)',
+    'bsx::k_wide_reduce_drain': 'wide networks: table to dense records, once per attract call',
+    'bsx::k_wide_reduce_target': 'wide networks: hits and first-hit histogram of a chunk (target summary)',
 }
 
 
