@@ -1,7 +1,9 @@
 """
-Wide-state family (networks of up to 1024 nodes, include/bsx.h BSX_MAX_NODES_WIDE).  The CPU oracle stops at 256
-nodes, so wide results are pinned by
-  * self-consistency: with BSX_WIDE=1 the golden vectors of the <= 256-node suite go through the wide kernels;
+Wide-state family (networks of up to 1024 nodes, include/bsx.h BSX_MAX_NODES_WIDE) at the sizes the CPU oracle
+reaches, and by composition.  The oracle stops at 256 nodes; above that the family is pinned against the exact
+numpy reference of tests/wide_ref.py by tests/test_gpu_wide_exact.py.  Here:
+  * self-consistency: with BSX_WIDE=1 the golden vectors and the oracle's cases of the <= 256-node suite go through
+    the wide kernels;
   * composition: a 512-node network made of two 256-node networks A and B with interleaved nodes, whose trajectories,
     lambda = lcm, mu = max and key follow from A and B on the oracle-pinned <= 256-node path;
   * the CLI on a 300-node network.
