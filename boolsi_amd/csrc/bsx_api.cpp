@@ -8,16 +8,14 @@
 #include <array>
 #include <chrono>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <unordered_map>
 #include <string>
 #include <vector>
 
+#include "bsx_cube_plan.h"
 #include "bsx_engine.h"
-
 #include "bsx_host.h"
-
 
 using namespace bsx;
 
@@ -87,8 +85,8 @@ extern "C" int bsx_create(bsx_handle* out, int device) {
     h->d_ctr = reinterpret_cast<Counters*>(h->d_ctr_raw.p + kLevelDescBytes);
     h->h_flag = reinterpret_cast<volatile uint32_t*>(h->h_ctr + kMaxChainBlocks);
     *h->h_flag = 0;
-    const char* cc_env = std::getenv("BSX_CYCLE_CACHE");       // "0" disables the cycle-state cache (A/B runs, tests)
-    h->cache_enabled = !(cc_env && cc_env[0] == '0');
+    h->knobs = Knobs::from_env();
+    h->cache_enabled = h->knobs.cycle_cache;        // BSX_CYCLE_CACHE=0 disables the cycle-state cache (A/B runs, tests)
     if ((e = h->d_cc_journal.alloc(kCycleJournalCap)) != hipSuccess ||
         (e = h->d_cc_claims.alloc(kCycleClaimSlots)) != hipSuccess || (e = h->d_cc_count.alloc(1)) != hipSuccess) {
         g_create_error = std::string("cycle cache allocation: ") + hipGetErrorString(e);
@@ -156,7 +154,8 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     if (!h) return BSX_ERR_INVALID;
     if (n_nodes == 0 || !pred_offsets || !tt_word_offsets || !tt_words)
         return fail(h, BSX_ERR_INVALID, "bsx_set_network: null table or zero nodes");
-    if (n_nodes > BSX_MAX_NODES || wide_forced())          // the wide-state family (bsx_wide_api.cpp)
+    h->knobs = Knobs::from_env();
+    if (n_nodes > BSX_MAX_NODES || h->knobs.wide)          // the wide-state family (bsx_wide_api.cpp)
         return wide_set_network(h, n_nodes, pred_offsets, pred_idx, tt_word_offsets, tt_words);
     wide_release(h);
     HIPCHK(h, hipSetDevice(h->device));
@@ -190,7 +189,7 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     const size_t cache_stride = ((2 * nw + 2 + 3) & ~3u) * 4;
     uint32_t slots = 1;
     size_t cache_lds = kCycleCacheLdsBytes;
-    if (const char* kb = std::getenv("BSX_CACHE_LDS_KB")) cache_lds = std::max<size_t>(1, (size_t)std::atoi(kb)) * 1024;   // tuning knob
+    if (h->knobs.cache_lds_kb) cache_lds = (size_t)h->knobs.cache_lds_kb * 1024;    // tuning knob
     while ((size_t)slots * 2 * cache_stride <= cache_lds) slots *= 2;
     h->cache_lds_slots = slots;
     const size_t cache_bytes = (size_t)slots * cache_stride + 16 + 16      // + header + alignment
@@ -200,8 +199,8 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     int lut_mode = 0;                                                       // kLutGlobal
     if (fixed_bytes + (size_t)nw * 4 * 256 * entry_bytes <= 144 * 1024) lut_mode = 1;                  // kLutLdsByte
     else if (nw >= 4 && fixed_bytes + (size_t)nw * 8 * 16 * entry_bytes <= 144 * 1024) lut_mode = 2;   // kLutLdsNibble
-    if (const char* m = std::getenv("BSX_LUT_MODE")) {                      // test knob: force a smaller-footprint mode
-        const int want = std::atoi(m);
+    if (h->knobs.lut_mode >= 0) {                                           // test knob: force a smaller-footprint mode
+        const int want = h->knobs.lut_mode;
         if (want == 0 || (want == 2 && nw >= 4 && fixed_bytes + (size_t)nw * 8 * 16 * entry_bytes <= 144 * 1024)) lut_mode = want;
     }
     const uint32_t chunk_bits = lut_mode == 2 ? 4 : 8, chunk_entries = 1u << chunk_bits;
@@ -247,10 +246,12 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     HIPCHK(h, h->d_wide_preds.upload(wpreds));
     HIPCHK(h, h->d_wide_tt.upload(wtt));
 
-    h->h_pred_offsets.assign(pred_offsets, pred_offsets + n_nodes + 1);
-    h->h_pred_idx.assign(pred_idx, pred_idx + pred_offsets[n_nodes]);
-    h->h_tt0.resize(n_nodes);
-    for (uint32_t i = 0; i < n_nodes; ++i) h->h_tt0[i] = tt_words[tt_word_offsets[i]];
+    h->model.n_nodes = n_nodes;
+    h->model.nw = nw;
+    h->model.pred_offsets.assign(pred_offsets, pred_offsets + n_nodes + 1);
+    h->model.pred_idx.assign(pred_idx, pred_idx + pred_offsets[n_nodes]);
+    h->model.tt0.resize(n_nodes);
+    for (uint32_t i = 0; i < n_nodes; ++i) h->model.tt0[i] = tt_words[tt_word_offsets[i]];
     h->n_nodes = n_nodes;
     h->w64 = (n_nodes + 63) / 64;
     h->net.n_nodes = n_nodes;
@@ -279,7 +280,7 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
         int blocks = 0;
         if (h->pool_ok) HIPCHK(h, configure_attract_pool((int)nw, (int)k_mux, h->lut_mode, std::min<size_t>(pool_max, 160 * 1024 - 1024), &blocks));
     }
-    if (std::getenv("BSX_DEBUG")) std::fprintf(stderr, "[bsx] network: nw %u k_mux %u lut mode %d (0 L2 bytes, 1 LDS bytes, 2 LDS nibbles) shmem %zu attract shmem %zu lean blocks/CU %d\n", nw, k_mux, (int)h->lut_mode, h->shmem, h->shmem_attract, h->lean_blocks_per_cu);
+    if (h->knobs.debug) std::fprintf(stderr, "[bsx] network: nw %u k_mux %u lut mode %d (0 L2 bytes, 1 LDS bytes, 2 LDS nibbles) shmem %zu attract shmem %zu lean blocks/CU %d\n", nw, k_mux, (int)h->lut_mode, h->shmem, h->shmem_attract, h->lean_blocks_per_cu);
     HIPCHK(h, configure_target((int)nw, (int)k_mux, h->lut_mode, h->shmem + 16 + kTargetHistBins * 8));
     HIPCHK(h, configure_simulate((int)nw, (int)k_mux, h->lut_mode, h->shmem));
     h->have_net = true;
@@ -350,11 +351,11 @@ extern "C" int bsx_set_problem_space(bsx_handle h, const uint64_t* origin_state_
         std::vector<std::array<uint32_t, 3>> ordered;
         for (uint32_t j = 0; j < n_sched; ++j) ordered.push_back({sched[j].t, sched[j].node, sched[j].value});
         std::stable_sort(ordered.begin(), ordered.end(), [](const auto& a, const auto& b) { return a[0] < b[0]; });
-        h->h_sched.clear();
-        for (const auto& e : ordered) { h->h_sched.push_back(e[0]); h->h_sched.push_back(e[1]); h->h_sched.push_back(e[2]); }
+        h->model.sched.clear();
+        for (const auto& e : ordered) { h->model.sched.push_back(e[0]); h->model.sched.push_back(e[1]); h->model.sched.push_back(e[2]); }
     }
-    h->h_any = any;
-    h->h_fv = fv;
+    h->model.any = any;
+    h->model.fv = fv;
     HIPCHK(h, h->d_any.upload(any));
     HIPCHK(h, h->d_fv.upload(fv));
     HIPCHK(h, h->d_pv.upload(pv));
@@ -365,11 +366,7 @@ extern "C" int bsx_set_problem_space(bsx_handle h, const uint64_t* origin_state_
     HIPCHK(h, hipMemset(h->d_cc_claims.p, 0, sizeof(unsigned int) * kCycleClaimSlots));
     HIPCHK(h, hipMemset(h->d_cc_count.p, 0, sizeof(unsigned int)));
     h->fast_ok = true;
-    h->split_cache.clear();
-    h->split_learned.clear();
-    h->split_regrown.clear();
-    std::memset(h->near_seen, 0, sizeof(h->near_seen));
-    h->cube_depth_cap = 0;
+    h->plan = PlanState();
     h->life_valid = 0;
     h->image_n = ~size_t(0);
     h->h_journal.clear();
@@ -514,6 +511,7 @@ extern "C" int bsx_run_target(bsx_handle h, const bsx_index* first, uint64_t cou
                               const uint64_t* mask_words, const uint64_t* code_words, bsx_hit* hits,
                               uint64_t cap, uint64_t* n_hits, bsx_stats* stats) {
     if (!h) return BSX_ERR_INVALID;
+    h->knobs = Knobs::from_env();
     if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
     if (!mask_words || !code_words || !n_hits || (cap && !hits)) return fail(h, BSX_ERR_INVALID, "null argument");
     if (int rc = check_range(h, first, count)) return rc;
@@ -574,6 +572,7 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
                                       uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
                                       uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats) {
     if (!h) return BSX_ERR_INVALID;
+    h->knobs = Knobs::from_env();
     if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
     if (!mask_words || !code_words || !n_hits || (cap && (!hits || !n_listed)) || (hist_bins && !hist))
         return fail(h, BSX_ERR_INVALID, "null argument");
@@ -588,7 +587,7 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (count == 0) return BSX_OK;
     if (count > (1ull << 40)) return fail(h, BSX_ERR_INVALID, "at most 2^40 problems per call");
-    if (h->wide && !wide_host_reduce())         // counted and binned on the device (bsx_wide_reduce.hip)
+    if (h->wide && !h->knobs.wide_host_reduce)         // counted and binned on the device (bsx_wide_reduce.hip)
         return wide_target_summary(h, first, count, max_t, mask_words, code_words, hist, hist_bins, hits, cap, n_hits, n_listed, stats);
     if (h->wide) {
         // BSX_WIDE_HOST_REDUCE=1: per-problem first-hit times of the wide kernel, summarised here (chunks of 2^24 problems)
@@ -649,8 +648,7 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
     }
     // the rest is only counted: cube passes over the aligned blocks of every fixed-node variant (the first update
     // of a block depends on its relevant digits only, build_cube), plain passes over what is left
-    const char* cubes_env = std::getenv("BSX_CUBES");
-    const bool cubes_ok = !(cubes_env && cubes_env[0] == '0') && h->sp.n_any >= kCubeMinBits && h->sp.n_any <= 64 &&
+    const bool cubes_ok = h->knobs.cubes && h->sp.n_any >= kCubeMinBits && h->sp.n_any <= 64 &&
                           (h->sp.identity_any || h->sp.n_runs) && !h->sp.n_pv && !h->sp.tp_origin && !h->variant_count_saturated;
     // The cube passes of a call are independent of each other -- one per aligned block and fixed-node variant, each a
     // short launch of one-class-per-lane searches that mostly waits (profiles/r03_pmc_config4.json: 90 % of the wave
@@ -684,7 +682,7 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
             const Counters& ctr = h->h_ctr_multi[i];
             total += ctr.log_cursor; steps_ref += ctr.steps_ref; steps_exec += ctr.steps_exec;
             ++launches; limit_hits += ctr.step_limit_hits;
-            if (std::getenv("BSX_DEBUG")) std::fprintf(stderr, "[bsx] target cube 2^%u, variant %llu: %u relevant digits (%zu launches side by side, %.3f ms together)\n", pending[i].a_bits, (unsigned long long)pending[i].variant, pending[i].rel, n, ms);
+            if (h->knobs.debug) std::fprintf(stderr, "[bsx] target cube 2^%u, variant %llu: %u relevant digits (%zu launches side by side, %.3f ms together)\n", pending[i].a_bits, (unsigned long long)pending[i].variant, pending[i].rel, n, ms);
         }
         pending.clear();
         return BSX_OK;
@@ -707,8 +705,8 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
         for (int w = 0; w < kMaxW32; ++w) { vfm[w] = h->sp.fixmask[w]; vfv[w] = h->sp.fixval[w]; }
         {   // the variant's fixed nodes (batching.py:171-175, 212-229)
             uint64_t v = variant;
-            for (size_t j = 0; j + 1 < h->h_fv.size(); j += 2) {
-                const uint32_t node = h->h_fv[j], range = h->h_fv[j + 1];
+            for (size_t j = 0; j + 1 < h->model.fv.size(); j += 2) {
+                const uint32_t node = h->model.fv[j], range = h->model.fv[j + 1];
                 const uint32_t radix = range == BSX_RANGE_MAYBE_TRUE_OR_FALSE ? 3 : 2, dg = (uint32_t)(v % radix);
                 v /= radix;
                 int st = -1;
@@ -733,9 +731,9 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
             while (a_bits > kCubeMinBits && ((at & (((unsigned __int128)1 << a_bits) - 1)) != 0 || at + ((unsigned __int128)1 << a_bits) > body_end)) --a_bits;
             const uint64_t block = 1ull << a_bits;
             Cube c;
-            build_cube(h, (uint64_t)at, a_bits, c, vfm);
+            build_cube(h->model, h->sp, (uint64_t)at, a_bits, c, vfm);
             if (c.ok && c.rel.size() + 2 <= a_bits) {
-                plan_cube(h, c);
+                plan_cube(h->model, h->sp, c);
                 TargetParams P{};
                 P.net = h->net;
                 P.sp = c.sp;
@@ -860,21 +858,21 @@ static int run_sim_sliced(bsx_handle h, const bsx_index* first, uint64_t count, 
     const uint32_t rows = (n + 15) & ~15u;     // node batch (4) x waves per workgroup (4)
     std::vector<uint32_t> desc((size_t)rows * 8, 0);
     for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t k = h->h_pred_offsets[i + 1] - h->h_pred_offsets[i];
-        for (uint32_t j = 0; j < k; ++j) desc[(size_t)i * 8 + j] = h->h_pred_idx[h->h_pred_offsets[i] + j];
+        const uint32_t k = h->model.pred_offsets[i + 1] - h->model.pred_offsets[i];
+        for (uint32_t j = 0; j < k; ++j) desc[(size_t)i * 8 + j] = h->model.pred_idx[h->model.pred_offsets[i] + j];
         uint64_t tt = 0;
         const bool fixed = (h->sp.fixmask[i >> 5] >> (i & 31)) & 1u;
         if (fixed) tt = ((h->sp.fixval[i >> 5] >> (i & 31)) & 1u) ? ~0ull : 0ull;     // model.py:45-47
         else
             for (uint32_t idx = 0; idx < (1u << K); ++idx)
-                if ((h->h_tt0[i] >> (idx & ((1u << k) - 1))) & 1ull) tt |= 1ull << idx;
+                if ((h->model.tt0[i] >> (idx & ((1u << k) - 1))) & 1ull) tt |= 1ull << idx;
         desc[(size_t)i * 8 + 6] = (uint32_t)tt;
         desc[(size_t)i * 8 + 7] = (uint32_t)(tt >> 32);
     }
     DevBuf<uint32_t> d_desc, d_sched;
     DevBuf<uint64_t> d_final, d_dig;
     HIPCHK(h, d_desc.upload(desc));
-    HIPCHK(h, d_sched.upload(h->h_sched));
+    HIPCHK(h, d_sched.upload(h->model.sched));
     if (final_states) HIPCHK(h, d_final.alloc(count * W));
     if (digests) HIPCHK(h, d_dig.alloc(count));
 
@@ -883,7 +881,7 @@ static int run_sim_sliced(bsx_handle h, const bsx_index* first, uint64_t count, 
     set_first(P.sp, first);
     P.n_nodes = n;
     P.n_rows = rows;
-    P.n_sched = (uint32_t)(h->h_sched.size() / 3);
+    P.n_sched = (uint32_t)(h->model.sched.size() / 3);
     P.w64 = W;
     P.desc = d_desc.p;
     P.sched = d_sched.p;
@@ -894,8 +892,7 @@ static int run_sim_sliced(bsx_handle h, const bsx_index* first, uint64_t count, 
     P.ctr = h->d_ctr;
 
     // K <= 3 and n <= 128: second-generation kernel (8-byte rows, constants in registers); BSX_SLICED=1 keeps the first
-    const char* sl_env = std::getenv("BSX_SLICED");
-    const bool gen2 = K <= 3 && rows <= 128 && !(sl_env && sl_env[0] == '1');
+    const bool gen2 = K <= 3 && rows <= 128 && h->knobs.sliced != 1;
     const size_t shmem = gen2 ? (size_t)rows * 1024 + (4096 + 64) * 4 : (size_t)rows * (8 + 128) * 4;
     const uint64_t groups = gen2 ? (count + 4095) / 4096 : (count + 2047) / 2048;
     const uint64_t per_cu = gen2 ? 1 : std::max<size_t>(1, (160 * 1024) / shmem);
@@ -927,16 +924,16 @@ extern "C" int bsx_run_simulate(bsx_handle h, const bsx_index* first, uint64_t c
                                 uint64_t* trajectories, uint64_t* final_states, uint64_t* digests,
                                 bsx_stats* stats) {
     if (!h) return BSX_ERR_INVALID;
+    h->knobs = Knobs::from_env();
     if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
     if (int rc = check_range(h, first, count)) return rc;
     if (int rc = check_max_t(h, max_t)) return rc;
     if (h->wide) return wide_run_simulate(h, first, count, max_t, trajectories, final_states, digests, stats);
     // Long fixed-length runs that only want final states go through the bit-sliced kernel
     // (BSX_SLICED=0 forces the per-lane kernel, for A/B runs and tests).
-    const char* sl_env = std::getenv("BSX_SLICED");
     // (digests: the second-generation kernel only, K <= 3 and n <= 128, which keeps them per row in registers)
-    const bool gen2_shape = h->net.k_mux <= 3 && ((h->n_nodes + 15) & ~15u) <= 128 && !(sl_env && sl_env[0] == '1');
-    const bool sliced_ok = !(sl_env && sl_env[0] == '0') && (final_states || digests) && !trajectories && (!digests || gen2_shape) &&
+    const bool gen2_shape = h->net.k_mux <= 3 && ((h->n_nodes + 15) & ~15u) <= 128 && h->knobs.sliced != 1;
+    const bool sliced_ok = h->knobs.sliced != 0 && (final_states || digests) && !trajectories && (!digests || gen2_shape) &&
                            !h->sp.n_fv && !h->sp.n_pv && !h->net.n_wide && max_t >= 64 && max_t < kStepLimit &&
                            count >= 2048 && (size_t)((h->n_nodes + 15) & ~15u) * 136 * 4 <= 160 * 1024;
     if (sliced_ok && count) return run_sim_sliced(h, first, count, max_t, final_states, digests, stats);
@@ -949,6 +946,7 @@ extern "C" int bsx_run_trajectories(bsx_handle h, const bsx_index* first, const 
                                     const uint64_t* t_len, uint64_t n, uint64_t* out,
                                     const uint64_t* out_offsets, bsx_stats* stats) {
     if (!h) return BSX_ERR_INVALID;
+    h->knobs = Knobs::from_env();
     if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
     if (n && (!offsets || !t_len || !out || !out_offsets)) return fail(h, BSX_ERR_INVALID, "null argument");
     uint64_t words = 0, tmax = 0, off_max = 0;

@@ -1,5 +1,6 @@
 // Shared host/device structures of the gfx950 engine (kernel parameters).  See DESIGN.md.
 #pragma once
+#include <cstddef>
 #include <stdint.h>
 
 namespace bsx {

@@ -1,5 +1,6 @@
-// Host-side internals shared by the translation units behind include/bsx.h (bsx_api.cpp, bsx_comm.cpp,
-// bsx_fgraph.hip): the engine handle, device buffers, error plumbing.  Not part of the ABI.
+// Host-side internals shared by the translation units behind include/bsx.h (bsx_api.cpp, bsx_attract_api.cpp,
+// bsx_cascade.cpp, bsx_fgraph_api.cpp, bsx_wide_api.cpp, bsx_comm.cpp): the engine handle, device buffers, error
+// plumbing.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,8 @@
 
 #include "bsx.h"
 #include "bsx_device.h"
+#include "bsx_knobs.h"
+#include "bsx_model.h"
 
 namespace bsx {
 
@@ -48,6 +51,7 @@ struct bsx_engine {
     hipDeviceProp_t prop{};
     double wall_clock_khz = 1e5;        // device clock behind wall_clock64()
     std::string error;
+    bsx::Knobs knobs;           // the environment as the current ABI call found it (bsx_knobs.h)
 
     // network
     bool have_net = false;
@@ -93,17 +97,12 @@ struct bsx_engine {
     bsx::LeafProgram* h_leaf = nullptr;     // ... its pinned staging copy
     uint32_t life_cache[64] = {};       // cube passes: k_digit_lifetimes per digit, measured on the first block that needed it
     uint64_t life_valid = 0;            // (an ordering heuristic: later blocks of the problem reuse it)
-    double near_seen[2][bsx::kMaxCubeLevels + 1][2] = {};   // cascade: [top level / below][depth] -> classes seen, of them near a cycle
-    uint32_t cube_depth_cap = 0;        // 0 = no experience yet; else the deepest level that paid off on this problem
+    bsx::PlanState plan;                // cascade: what the planner has learned about this problem space (bsx_model.h)
     bsx::DevBuf<uint32_t> d_life;       // cube collapse: per-digit influence lifetimes (ordering heuristic)
     bsx::DevBuf<uint32_t> d_lut, d_masks, d_wide_desc, d_wide_preds, d_wide_tt;
 
-    // host copies for the bit-sliced simulate kernel's node descriptors
-    std::vector<uint32_t> h_pred_offsets, h_pred_idx;
-    std::vector<uint64_t> h_tt0;        // first table word of every node (all of it when k <= 6)
-    std::vector<uint32_t> h_sched;      // origin perturbations (t, node, value), sorted by t
-    std::vector<uint32_t> h_any;        // 'any' nodes in digit order (cube collapse: relevant-digit analysis)
-    std::vector<uint32_t> h_fv;         // fixed-node variations (node, range) in digit order
+    // host copies of the network and the space: the cube planner's input, the sliced simulate kernel's node descriptors
+    bsx::HostModel model;
 
     // problem space
     bool have_space = false;
@@ -127,9 +126,6 @@ struct bsx_engine {
     hipEvent_t ev_top0 = nullptr, ev_top1 = nullptr;
     std::vector<bsx::Counters> ctr_seen;                // the counter blocks of the last batch of chains, as fetched
     std::vector<hipEvent_t> ev_chain;                   // pairs around the top-level (dominant) launch of every chain of a batch
-    std::map<uint32_t, uint32_t> split_regrown;         // ... how often it was regrown because it did not fit a block
-    std::map<uint32_t, double> split_learned;           // ... and how many classes' listing the handle had seen when it was grown (near_seen)
-    std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> split_cache;    // block size -> leaves (fix mask, values) of its split tree
     // independent launches of one call side by side (target's cube passes): auxiliary streams, one counter block per launch
     hipStream_t aux[8] = {};
     hipEvent_t aux_done[8] = {};
@@ -159,8 +155,6 @@ struct bsx_engine {
     } while (0)
 
 namespace bsx {
-bool wide_forced();
-bool wide_host_reduce();        // BSX_WIDE_HOST_REDUCE=1
 void wide_release(bsx_handle h);
 int wide_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* pred_offsets, const uint32_t* pred_idx,
                      const uint32_t* tt_word_offsets, const uint64_t* tt_words);

@@ -1,6 +1,6 @@
 // Host-side helpers shared by the translation units behind include/bsx.h (bsx_api.cpp: handle, network, problem
-// space, target, simulate; bsx_attract_api.cpp: attract): kernel launch prototypes, range checks, wide integers for
-// the sums of sweeps beyond 2^64 problems, the cube analysis.  Not part of the ABI.
+// space, target, simulate; bsx_attract_host.h: attract; bsx_wide_api.cpp): kernel launch prototypes, range checks,
+// index arithmetic.  Not part of the ABI.  (Wide integers and the merge: bsx_merge.h; the cube analysis: bsx_cube_plan.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "bsx_engine.h"
+#include "bsx_merge.h"
 
 namespace bsx {
 hipError_t launch_attract(int nw, int k, int lut_mode, dim3 grid, size_t shmem, hipStream_t st, const AttractParams& P);
@@ -50,8 +51,6 @@ hipError_t configure_simulate(int nw, int k, int lut_mode, size_t shmem);
 }  // namespace bsx
 
 namespace bsx {
-
-typedef unsigned __int128 u128;
 
 struct Launch {
     dim3 grid;
@@ -144,98 +143,5 @@ inline double now_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
-
-// ---- wide unsigned integers: counts and sums of sweeps over more than 2^64 problems ------------------------------
-struct U256 {
-    uint64_t w[4] = {0, 0, 0, 0};
-    void add_at(uint64_t v, int word) {                     // += v << (64 * word)
-        for (int i = word; i < 4 && v; ++i) { const uint64_t s = w[i] + v; v = s < v ? 1 : 0; w[i] = s; }
-    }
-    void add(const U256& o) {
-        uint64_t carry = 0;
-        for (int i = 0; i < 4; ++i) {
-            const u128 s = (u128)w[i] + o.w[i] + carry;
-            w[i] = (uint64_t)s; carry = (uint64_t)(s >> 64);
-        }
-    }
-    void add128(u128 v) { U256 t; t.w[0] = (uint64_t)v; t.w[1] = (uint64_t)(v >> 64); add(t); }
-    // += (hi:lo) << shift, shift < 128
-    void add_shifted(uint64_t lo, uint64_t hi, uint32_t shift) {
-        U256 t;
-        t.w[0] = lo; t.w[1] = hi;
-        const uint32_t ws = shift >> 6, bs = shift & 63;
-        U256 r;
-        for (int i = 3; i >= 0; --i) {
-            const int src = i - (int)ws;
-            uint64_t v = 0;
-            if (src >= 0) v = t.w[src] << bs;
-            if (bs && src - 1 >= 0) v |= t.w[src - 1] >> (64 - bs);
-            r.w[i] = v;
-        }
-        add(r);
-    }
-    // += sign-extended v (two's complement): the result is known to be non-negative
-    void add_signed(int64_t v) {
-        U256 t;
-        t.w[0] = (uint64_t)v;
-        t.w[1] = t.w[2] = t.w[3] = v < 0 ? ~0ull : 0ull;
-        add(t);
-    }
-    // += a * b
-    void add_mul(u128 a, uint64_t b) {
-        const u128 p0 = (u128)(uint64_t)a * b, p1 = (u128)(uint64_t)(a >> 64) * b;
-        U256 t;
-        t.w[0] = (uint64_t)p0;
-        const u128 mid = (p0 >> 64) + (uint64_t)p1;
-        t.w[1] = (uint64_t)mid;
-        t.w[2] = (uint64_t)((mid >> 64) + (uint64_t)(p1 >> 64));
-        add(t);
-    }
-    bool fits(int words) const { for (int i = words; i < 4; ++i) if (w[i]) return false; return true; }
-};
-
-// One aggregated attractor inside the library (every sum wide; narrowed to the caller's record at the boundary).
-struct WideRec {
-    uint64_t key[BSX_MAX_WORDS] = {0, 0, 0, 0};
-    uint64_t length = 0;
-    u128 count = 0;
-    U256 sum_l, sum_l2;
-};
-
-// attractor key as the table key of the host-side merge (zero padded to the longest state)
-using Key8 = std::array<uint32_t, kMaxW32>;
-struct Key8Hash {
-    size_t operator()(const Key8& k) const {
-        uint64_t h = 0x9E3779B97F4A7C15ull;
-        for (uint32_t w : k) h = (h ^ w) * 0xBF58476D1CE4E5B9ull;
-        return (size_t)(h ^ (h >> 29));
-    }
-};
-inline Key8 key8(const uint32_t* words) { Key8 k; std::copy(words, words + kMaxW32, k.begin()); return k; }
-
-// ---- cube collapse: which of the `a` lowest initial-state digits can the FIRST update of the
-// block starting at digit value d_lo depend on?  (bsx_attract_api.cpp: build_cube / plan_cube; target's summary
-// passes use them too)
-struct Cube {
-    uint64_t d_lo;              // first digit value (multiple of 2^a)
-    uint32_t a;                 // log2 of the problems in the block
-    // A SUB-BLOCK fixes some of the block's a lowest digits as well (fix_mask / fix_vals over the digit index): the block is the
-    // disjoint union of the sub-blocks of a split, and fixing a well-chosen digit makes many others irrelevant
-    // (bsx_attract_api.cpp: plan_split).  free_digits = the digits that vary, n_free of them: the sub-block has 2^n_free problems.
-    uint64_t fix_mask = 0, fix_vals = 0, free_digits = 0;
-    uint32_t n_free = 0;
-    std::vector<uint32_t> rel;  // relevant digits: ascending from build_cube, then in class-index bit order
-    uint32_t base[kMaxW32];     // the block's fixed bits, free bits zero
-    DevSpace sp;                // enumeration of the relevant digits' assignments (plan_cube)
-    uint32_t umask[kMaxW32];    // node bits of the irrelevant free digits
-    uint32_t free_mask[kMaxW32];
-    bool ok = false;            // false: more deposit runs than the kernels take
-};
-void build_cube(const bsx_engine* h, uint64_t d_lo, uint32_t a, Cube& c, const uint32_t* fixmask = nullptr,
-                uint64_t fix_mask = 0, uint64_t fix_vals = 0);
-void plan_cube(const bsx_engine* h, Cube& c);
-
-constexpr uint32_t kCubeMinBits = 16;           // cube collapse: smallest aligned block handled as a cube
-constexpr uint32_t kCubeMaxBits = 63;           // ... and the largest (member counts are 64-bit; a 2^64 space is two blocks)
 
 }  // namespace bsx

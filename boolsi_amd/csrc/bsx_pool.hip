@@ -7,7 +7,7 @@ namespace bsx {
 constexpr int kPoolWaves = kPoolBlockThreads / 64;
 
 // Last kernel of a chain: the counter blocks -> pinned host memory, then (system-scope release) the sequence number
-// the host is spinning on (bsx_attract_api.cpp: fetch_counters).
+// the host is spinning on (bsx_cascade.cpp: fetch_counters).
 __global__ __launch_bounds__(256) void k_publish(const uint32_t* src, uint32_t* host_dst, uint32_t words, uint32_t* host_flag, uint32_t seq,
                                                   unsigned int* ticket) {
     // (the blocks are multiples of 256 bytes: whole uint4s)

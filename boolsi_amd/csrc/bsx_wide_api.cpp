@@ -3,7 +3,6 @@
 // bsx_api.cpp hands a handle over here when its network has more than BSX_MAX_NODES nodes (or BSX_WIDE=1).
 #include <algorithm>
 #include <array>
-#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <vector>
@@ -45,24 +44,13 @@ struct WideHost {
     size_t shmem = 0;
 };
 
-bool wide_forced() {
-    const char* e = std::getenv("BSX_WIDE");
-    return e && e[0] == '1';
-}
-
-// BSX_WIDE_HOST_REDUCE=1: per-problem records and hit times are copied back and reduced on the host, chunk by chunk
-// (the path before bsx_wide_reduce.hip; kept for A/B runs and tests).
-bool wide_host_reduce() {
-    const char* e = std::getenv("BSX_WIDE_HOST_REDUCE");
-    return e && e[0] == '1';
-}
+// (BSX_WIDE_HOST_REDUCE=1: per-problem records and hit times are copied back and reduced on the host, chunk by chunk --
+// the path before bsx_wide_reduce.hip; kept for A/B runs and tests.)
 
 // Problems per k_wide launch of a chunked run: BSX_WIDE_CHUNK clamped to [32 * L, 2^18], else `dflt`.
-static uint64_t wide_chunk(const WideHost& W, uint64_t dflt) {
-    const char* e = std::getenv("BSX_WIDE_CHUNK");
-    if (!e || !e[0]) return dflt;
-    const uint64_t v = std::strtoull(e, nullptr, 10);
-    return std::max<uint64_t>(32ull * W.L, std::min<uint64_t>(v, 1ull << 18));
+static uint64_t wide_chunk(const bsx_engine* h, uint64_t dflt) {
+    if (!h->knobs.wide_chunk_set) return dflt;
+    return std::max<uint64_t>(32ull * h->wide->L, std::min<uint64_t>(h->knobs.wide_chunk, 1ull << 18));
 }
 
 void wide_release(bsx_handle h) {
@@ -257,8 +245,7 @@ static int wide_enqueue(bsx_handle h, WideParams& P, const bsx_index* first, uin
     P.count = count;
     P.max_t = max_t;
     P.cap_inf = max_t == BSX_T_INF ? 1u : 0u;
-    P.step_limit = kWideStepLimit;
-    if (const char* e = std::getenv("BSX_WIDE_STEP_LIMIT")) P.step_limit = std::max(16u, std::min(kWideStepLimit, (uint32_t)std::atoi(e)));
+    P.step_limit = h->knobs.wide_step_limit;        // kWideStepLimit unless BSX_WIDE_STEP_LIMIT says less
     if (W.wdesc.empty()) P.wdesc = nullptr;
     P.ctr = W.d_ctr.p;
     const uint32_t G = 32 * W.L;
@@ -387,7 +374,7 @@ int wide_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, ui
         if ((mask_words[i >> 6] >> (i & 63)) & 1ull) P0.tmask[i >> 5] |= 1u << (i & 31);
         if ((code_words[i >> 6] >> (i & 63)) & 1ull) P0.tcode[i >> 5] |= 1u << (i & 31);
     }
-    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(W, 1ull << 24));
+    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(h, 1ull << 24));
     const uint32_t bins_alloc = std::max<uint32_t>(hist_bins, 1);
     HIPCHK(h, W.d_thit.reserve(chunk));
     HIPCHK(h, W.d_hist.reserve(bins_alloc));
@@ -543,6 +530,7 @@ extern "C" int bsx_run_attract_wide(bsx_handle h, bsx_u128 first_flat, bsx_u128 
                                     bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor,
                                     bsx_stats2* stats) {
     if (!h) return BSX_ERR_INVALID;
+    h->knobs = Knobs::from_env();
     if (!table || !n_out) return fail(h, BSX_ERR_INVALID, "table / n_out is null");
     if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
     if (!h->wide) {
@@ -584,10 +572,10 @@ extern "C" int bsx_run_attract_wide(bsx_handle h, bsx_u128 first_flat, bsx_u128 
     if (count == 0) return BSX_OK;
     HIPCHK(h, hipSetDevice(h->device));
     WideHost& W = *h->wide;
-    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(W, 1ull << 18));
+    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(h, 1ull << 18));
     // (more than kWideReduceMaxCap possible attractors: the device table would take gigabytes; such a call is reduced
     // on the host, which allocates per attractor found)
-    if (!wide_host_reduce() && std::min<uint64_t>(cap, count) <= kWideReduceMaxCap) return attract_wide_device(h, first, count, chunk, max_t, max_len, table, cap, n_out, n_no_attractor, stats, t_begin);
+    if (!h->knobs.wide_host_reduce && std::min<uint64_t>(cap, count) <= kWideReduceMaxCap) return attract_wide_device(h, first, count, chunk, max_t, max_len, table, cap, n_out, n_no_attractor, stats, t_begin);
     // BSX_WIDE_HOST_REDUCE=1 (or a table beyond kWideReduceMaxCap): every chunk's records come back and are aggregated here by key
     DevBuf<uint32_t> d_info;
     DevBuf<uint64_t> d_keys;
