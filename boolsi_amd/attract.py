@@ -25,13 +25,14 @@ from .model import decode_state
 class AggregatedAttractor:
     """Attractor with its basin statistics (reference attract.py:18-45)."""
 
-    def __init__(self, key, length, frequency, sum_l, sum_l2, states=None):
+    def __init__(self, key, length, frequency, sum_l, sum_l2, states=None, activity=None):
         self.key = key
         self.length = length
         self.frequency = frequency
         self.sum_l = sum_l
         self.sum_l2 = sum_l2
-        self.states = states        # list of lists of bool, first state = key state
+        self.states = states        # list of lists of bool, first state = key state; None when they were not asked for
+        self.activity = activity    # float64 per node: the share of the attractor's states in which it is on; or None
 
     @property
     def trajectory_l_mean(self):
@@ -144,11 +145,13 @@ def run_attract_range(engine, first, count, max_t=inf, max_attractor_l=inf, cap=
 
 def attract_master(engine, origin_simulation_problem, simulation_problem_variations,
                    predecessor_node_lists, truth_tables, max_t, max_attractor_l,
-                   n_simulation_problems, comm=None, with_states=True):
+                   n_simulation_problems, comm=None, with_states=True, with_activity=False):
     """
     Attract over the whole problem space, range-partitioned over `comm` (one rank per GPU).
     Returns (list of AggregatedAttractor in final order, n_no_attractor, total_frequency, stats);
     identical on every rank.  Log lines follow attract.py:95-138.
+    with_states / with_activity: list every attractor's states / its nodes' mean activity (what the node
+    correlations need); both come from batched device calls over the ordered table (profile_attractors).
     """
     comm = comm or Comm()
     log = logging.getLogger()
@@ -191,20 +194,47 @@ def attract_master(engine, origin_simulation_problem, simulation_problem_variati
         log.info(' '.join(parts))
 
     order = sorted(merged.items(), key=lambda kv: (-kv[1][1], kv[0]))     # attract.py:170-173
-    attractors = []
-    for key, (length, freq, s1, s2) in order:
-        states = None
-        if with_states:
-            states = cycle_states(engine, key, length)
-        attractors.append(AggregatedAttractor(key, length, freq, s1, s2, states))
+    attractors = [AggregatedAttractor(key, length, freq, s1, s2) for key, (length, freq, s1, s2) in order]
+    if with_states or with_activity:
+        profile_attractors(engine, attractors, with_states, with_activity)
     return attractors, none, total_frequency, stats
 
 
-def cycle_states(engine, key, length):
+# One profile call's share of the table: its states stay within this many node states (a 64th of what a whole table may
+# hold, MAX_STATE_CELLS), its on-counts within as many counters.
+PROFILE_CHUNK_CELLS = 1 << 25
+
+
+def profile_attractors(engine, attractors, with_states=True, with_activity=True):
     """
-    States of the attractor, starting at its key state (attract.py:22-25 rotation).  Regenerated on
-    the device by stepping from the key under the origin problem's fixed nodes (attract mode allows
-    no fixed-node variations, input.py:392-397, so every problem shares them).
+    Fills .states and / or .activity of every attractor from batched device calls (Engine.attractor_profile), chunked
+    so that one call's output stays within PROFILE_CHUNK_CELLS.  An attractor whose walk from the key does not close
+    after its length is an error, as an attractor reported with two lengths is in merge_tables.
     """
-    states = engine.states_from(key, length - 1)
-    return [decode_state(words_to_code(s), engine.net.n_nodes) for s in states]
+    from .simulate import MAX_STATE_CELLS
+    n_nodes = engine.net.n_nodes
+    if with_states:
+        cells = sum(a.length for a in attractors) * n_nodes
+        if cells > MAX_STATE_CELLS:
+            raise ValueError('{} attractors were found; their {} node states do not fit in host memory -- use -x '
+                             '(no attractor output): the node correlations need no states'.format(len(attractors), cells))
+    lo = 0
+    while lo < len(attractors):
+        hi, cells = lo, 0
+        while hi < len(attractors):
+            cost = (attractors[hi].length if with_states else 1) * n_nodes
+            if hi > lo and cells + cost > PROFILE_CHUNK_CELLS:
+                break
+            cells += cost
+            hi += 1
+        part = attractors[lo:hi]
+        on_counts, states, closed = engine.attractor_profile([a.key for a in part], [a.length for a in part],
+                                                             states=with_states, activity=with_activity)
+        for q, a in enumerate(part):
+            if not closed[q]:
+                raise RuntimeError('attractor {} does not return to its key state after {} steps'.format(a.key, a.length))
+            if with_states:
+                a.states = [decode_state(words_to_code(s), n_nodes) for s in states[q]]
+            if with_activity:
+                a.activity = on_counts[q].astype(np.float64) / a.length
+        lo = hi

@@ -40,12 +40,15 @@ def compute_frequency_spearmanrho(data, frequencies):
 
 
 def find_node_correlations(attractors):
-    """attractors: list of AggregatedAttractor with .states and .frequency -> (Rho, P) or None."""
+    """attractors: list of AggregatedAttractor with .frequency and .activity or .states -> (Rho, P) or None.
+    An observation is a node's mean state over the attractor: .activity (on-counts / length, from the device) where it
+    is there, else the mean over .states -- the same float64, an exact integer sum divided by the length."""
     total = sum(a.frequency for a in attractors)
     if len(attractors) == 1 or total <= 2:
         logging.getLogger().info('Not enough attractors to infer node correlations.')
         return None
-    observations = np.array([np.mean(np.array(a.states, dtype=float), axis=0) for a in attractors])
+    observations = np.array([a.activity if getattr(a, 'activity', None) is not None else
+                             np.mean(np.array(a.states, dtype=float), axis=0) for a in attractors])
     frequencies = np.array([a.frequency for a in attractors])
     logging.getLogger().info('Computing node correlations...')
     return compute_frequency_spearmanrho(observations, frequencies)

@@ -184,7 +184,8 @@ def attract(**kw):
         attractors, n_none, total_frequency, stats = attract_master(
             run.open_engine(), cfg['origin simulation problem'], cfg['simulation problem variations'],
             cfg['incoming node lists'], cfg['truth tables'], max_t, max_len,
-            cfg['total combination count'], comm=run.comm)
+            cfg['total combination count'], comm=run.comm,
+            with_states=not kw['no_attractor_output'], with_activity=not kw['no_node_correlations'])
         if run.comm.rank != 0:
             return
         logging.getLogger().info(

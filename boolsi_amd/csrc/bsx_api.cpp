@@ -283,6 +283,7 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     if (h->knobs.debug) std::fprintf(stderr, "[bsx] network: nw %u k_mux %u lut mode %d (0 L2 bytes, 1 LDS bytes, 2 LDS nibbles) shmem %zu attract shmem %zu lean blocks/CU %d\n", nw, k_mux, (int)h->lut_mode, h->shmem, h->shmem_attract, h->lean_blocks_per_cu);
     HIPCHK(h, configure_target((int)nw, (int)k_mux, h->lut_mode, h->shmem + 16 + kTargetHistBins * 8));
     HIPCHK(h, configure_simulate((int)nw, (int)k_mux, h->lut_mode, h->shmem));
+    HIPCHK(h, configure_profile((int)nw, (int)k_mux, h->lut_mode, h->shmem));
     h->have_net = true;
     return BSX_OK;
 }

@@ -333,6 +333,29 @@ struct SimParams {
     Counters* ctr;
 };
 
+// Attractor profile (bsx_profile.hip): lane q walks `lengths[q]` states from the explicit state keys[q] under the
+// origin's fixed nodes (no schedule, no variations) and leaves per-node on-counts, the states, and whether the walk
+// came back to the key.  The host has checked every length, key and offset before the launch.
+// Workgroup size: 8-word states with 5 or 6 mux levels need more than the 256 registers a lane of a 512-thread
+// workgroup can have (the mux tree alone holds 2^(K-1) * NW words, and the on-count planes 8 * NW more), so NW = 8 runs
+// 256 threads per workgroup -- one wave per SIMD, the unified register file to itself -- and nothing goes to scratch.
+constexpr int profile_block(int nw) { return nw == 8 ? 256 : kBlock; }
+struct ProfileParams {
+    DevNet net;
+    uint32_t fixmask[kMaxW32];
+    uint32_t fixval[kMaxW32];
+    uint64_t count;
+    uint32_t w64;               // uint64 words per state
+    uint32_t key_stride;        // uint64 words per row of `keys` (>= w64)
+    const uint64_t* keys;       // [count][key_stride]
+    const uint64_t* lengths;    // [count], 1 <= length < kStepLimit
+    const uint64_t* state_offsets;  // [count] word offset of attractor q's states (with `states`)
+    uint32_t* on_counts;        // nullable: [count][n_nodes], zeroed by the host
+    uint64_t* states;           // nullable
+    uint8_t* closed;            // nullable: [count]
+    Counters* ctr;
+};
+
 // Bit-sliced simulate kernel (fixed-length runs, no per-problem variations): one lane owns 32
 // trajectories, the state is an n x 64-lane matrix of 32-bit words in LDS, double buffered.
 struct SlicedParams {

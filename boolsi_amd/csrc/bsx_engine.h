@@ -170,6 +170,9 @@ int wide_target_times(bsx_handle h, const bsx_index* first, uint64_t count, uint
 int wide_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
                         const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
                         uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats);
+int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
+                     uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
+                     uint64_t sum_len, bsx_stats* stats);
 }  // namespace bsx
 
 static inline int fail(bsx_handle h, int status, const std::string& msg) {

@@ -48,6 +48,8 @@ size_t fg_cyc_entry_bytes();
 hipError_t launch_table_drain(LogRec* tab, uint64_t slots, LogRec* out, uint64_t out_cap, unsigned long long* cursor, hipStream_t st);
 hipError_t configure_target(int nw, int k, int lut_mode, size_t shmem);
 hipError_t configure_simulate(int nw, int k, int lut_mode, size_t shmem);
+hipError_t launch_profile(int nw, int k, int lut_mode, dim3 grid, size_t shmem, hipStream_t st, const ProfileParams& P);
+hipError_t configure_profile(int nw, int k, int lut_mode, size_t shmem);
 }  // namespace bsx
 
 namespace bsx {

@@ -62,6 +62,30 @@ struct WideParams {
     unsigned long long* ctr;    // [0] reference steps, [1] executed trajectory updates, [2] step-limit hits
 };
 
+// ---- attractor profile (k_wide_profile in bsx_wide.hip, bsx_run_attractor_profile) ----
+// A group of 32 * L attractors walks in lock step from its key states, bit b live while t < length_b and frozen after
+// (so the matrix ends at f^length(key) for every bit); `net` carries the network part of WideParams (layout, row
+// descriptors, n_fslots) and nothing of a problem space: origin fixed nodes are constant rules in the descriptors.
+// Rows a thread owns: rows * L / kWideThreads, at most 36 for the L that wide_lds_words admits.
+constexpr uint32_t kWideProfileRows = 36;
+struct WideProfileParams {
+    WideParams net;
+    uint64_t count;
+    uint32_t key_stride;            // uint64 words per row of `keys` (>= w64)
+    uint32_t pad;
+    const uint64_t* keys;           // [count][key_stride]
+    const uint64_t* lengths;        // [count], checked by the host
+    const uint64_t* state_offsets;  // [count] (with `states`)
+    uint32_t* on_counts;            // nullable: [count][n_nodes], zeroed by the host
+    uint64_t* states;               // nullable
+    uint8_t* closed;                // nullable: [count]
+    unsigned long long* ctr;        // [1] executed trajectory updates
+};
+// LDS words of k_wide_profile: two matrices, the (zero) fixed-variation masks, partials, live masks, lengths.
+inline uint32_t wide_profile_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslots) {
+    return 2 * rows * L + 2 * n_fslots * L + kWideThreads + 2 * L + 32 * L + 8;
+}
+
 // ---- device-side reduction of the kernel's per-problem records (bsx_wide_reduce.hip) ----
 // Attract: an open-addressing HBM table keyed by the whole w64-word key, linear probing.
 // Widths of the sums, for at most 2^64 - 1 problems per call (bsx_run_attract_wide refuses more) and

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bsx_device.h"
+#include "bsx_planes.h"
 #include "bsx_wide.h"
 
 namespace bsx {
@@ -538,6 +539,171 @@ hipError_t launch_wide(int k, dim3 grid, size_t shmem, hipStream_t st, const Wid
         case 4: return launch_wide_k<4>(grid, shmem, st, P);
         case 5: return launch_wide_k<5>(grid, shmem, st, P);
         case 6: return launch_wide_k<6>(grid, shmem, st, P);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Attractor profile (bsx_run_attractor_profile on the wide family; layout and step function of k_wide).
+namespace {
+
+typedef Planes<(int)kWideProfileRows, kWideProfilePlanes> WidePlanes;
+
+// Calls f(r, word) for every row r this thread owns: bit b of word = node r's bit in the key of attractor 32 c + b of
+// the group (0 beyond n_valid and for padding rows).  The 32 key words of a 64-row block are loaded once per block.
+template <typename F>
+__device__ __forceinline__ void wide_key_rows(const WideProfileParams& Q, const WideCtx& X, uint64_t base, uint32_t n_valid, F f) {
+    uint64_t kw[32];
+    uint32_t have = kWideNone;
+    for (uint32_t r = X.r0; r < X.r1; ++r) {
+        if ((r >> 6) != have) {
+            have = r >> 6;
+#pragma unroll
+            for (int b = 0; b < 32; ++b) {
+                const uint32_t k = 32u * X.c + (uint32_t)b;
+                kw[b] = (k < n_valid && have < Q.net.w64) ? Q.keys[(base + k) * Q.key_stride + have] : 0ull;
+            }
+        }
+        uint32_t word = 0;
+#pragma unroll
+        for (int b = 0; b < 32; ++b) word |= (uint32_t)((kw[b] >> (r & 63u)) & 1ull) << b;
+        f(r, r < Q.net.n_nodes ? word : 0u);
+    }
+}
+
+// on_counts[attractor 32 c + b][node r0 + I] += count of bit b of owned row I; one owner per (attractor, node)
+template <int I>
+__device__ __forceinline__ void wide_flush_rows(const WidePlanes& pl, const WideProfileParams& Q, const WideCtx& X, uint64_t base,
+                                                uint32_t n_valid) {
+    const uint32_t r = X.r0 + (uint32_t)I;
+    if ((uint32_t)I < Q.net.rows_ps && r < Q.net.n_nodes) {
+        for (uint32_t b = 0; b < 32u; ++b) {
+            const uint32_t k = 32u * X.c + b;
+            const uint32_t cnt = planes_count_at<I>(pl, b);
+            if (k < n_valid && cnt) Q.on_counts[(base + k) * Q.net.n_nodes + r] += cnt;
+        }
+    }
+    if constexpr (I + 1 < (int)kWideProfileRows) wide_flush_rows<I + 1>(pl, Q, X, base, n_valid);
+}
+
+}  // namespace
+
+template <int K, bool KW>
+__global__ __launch_bounds__(kWideThreads) void k_wide_profile(const WideProfileParams Q) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
+    const WideParams& P = Q.net;
+    WideCtx X;
+    X.L = P.L;
+    X.tid = threadIdx.x;
+    X.c = X.tid & (P.L - 1);
+    X.slice = X.tid >> P.lshift;
+    X.r0 = X.slice * P.rows_ps;
+    X.r1 = X.r0 + P.rows_ps;
+    X.RL = P.rows * P.L;
+    const uint32_t L = P.L, c = X.c, RL = X.RL, G = 32 * L, tid = X.tid;
+    const uint32_t nslices = kWideThreads / L;
+    uint32_t* cur = sm;
+    uint32_t* nxt = sm + RL;
+    uint32_t* fmv = sm + 2 * RL;                    // [n_fslots][2][L]  all zero: no variations here
+    uint32_t* red = fmv + 2 * P.n_fslots * L;       // [256]             per-thread partials
+    uint32_t* col = red + kWideThreads;             // [2][L]            live masks of step t and t + 1
+    uint32_t* len = col + 2 * L;                    // [G]               lengths (0 beyond n_valid)
+    uint32_t* misc = len + G;                       // [8]
+    unsigned long long steps_exec = 0;
+    for (uint32_t i = tid; i < 2 * P.n_fslots * L; i += kWideThreads) fmv[i] = 0;
+
+    const uint64_t n_groups = (Q.count + G - 1) / G;
+    for (uint64_t group = blockIdx.x; group < n_groups; group += gridDim.x) {
+        const uint64_t base = group * G;
+        const uint32_t n_valid = (uint32_t)((Q.count - base) < G ? (Q.count - base) : G);
+        if (tid < 8) misc[tid] = 0;
+        __syncthreads();
+        // ---- lengths, and the keys deposited into the matrix
+        for (uint32_t k = tid; k < G; k += kWideThreads) {
+            const uint32_t l = k < n_valid ? (uint32_t)Q.lengths[base + k] : 0u;
+            len[k] = l;
+            if (l) atomicMax(&misc[0], l);
+        }
+        wide_key_rows(Q, X, base, n_valid, [&](uint32_t r, uint32_t word) { cur[r * L + c] = word; });
+        __syncthreads();
+        const uint32_t lam_max = misc[0];
+        if (tid < L) {
+            uint32_t act = 0;
+            for (uint32_t b = 0; b < 32; ++b) act |= (len[32 * tid + b] ? 1u : 0u) << b;
+            col[tid] = act;
+        }
+        __syncthreads();
+        // ---- the walk: bit b counts, is stored and advances while t < length_b
+        WidePlanes pl;
+        planes_clear(pl);
+        uint32_t pending = 0;
+        for (uint32_t t = 0; t < lam_max; ++t) {
+            const uint32_t live = col[(t & 1u) * L + c];
+            if (Q.on_counts) {
+                uint32_t v[kWideProfileRows];
+#pragma unroll
+                for (int i = 0; i < (int)kWideProfileRows; ++i) v[i] = (uint32_t)i < P.rows_ps ? cur[(X.r0 + (uint32_t)i) * L + c] & live : 0u;
+                planes_add(pl, v);
+                if (++pending == WidePlanes::kFlushEvery) {
+                    wide_flush_rows<0>(pl, Q, X, base, n_valid);
+                    planes_clear(pl);
+                    pending = 0;
+                }
+            }
+            if (Q.states) {
+                for (uint32_t i = tid; i < n_valid * P.w64; i += kWideThreads) {
+                    const uint32_t k = i / P.w64, w = i % P.w64;
+                    if (t < len[k]) Q.states[Q.state_offsets[base + k] + (uint64_t)t * P.w64 + w] = wide_gather64(P, cur, L, k, w);
+                }
+            }
+            wide_step<K, KW>(P, X, cur, nxt, fmv, live);
+            if (tid < L) {
+                uint32_t act = 0;
+                for (uint32_t b = 0; b < 32; ++b) act |= (t + 1 < len[32 * tid + b] ? 1u : 0u) << b;
+                col[((t + 1) & 1u) * L + tid] = act;
+            }
+            __syncthreads();
+            uint32_t* s = cur; cur = nxt; nxt = s;
+        }
+        if (Q.on_counts && pending) wide_flush_rows<0>(pl, Q, X, base, n_valid);
+        // ---- closed: bit b was frozen at f^length_b(key_b); no row may differ from the key in that bit
+        if (Q.closed) {
+            uint32_t diff = 0;
+            wide_key_rows(Q, X, base, n_valid, [&](uint32_t r, uint32_t word) { diff |= word ^ cur[r * L + c]; });
+            red[tid] = diff;
+            __syncthreads();
+            if (tid < L) {
+                uint32_t df = 0;
+                for (uint32_t s = 0; s < nslices; ++s) df |= red[s * L + tid];
+                for (uint32_t b = 0; b < 32; ++b) {
+                    const uint32_t k = 32 * tid + b;
+                    if (k < n_valid) Q.closed[base + k] = ((df >> b) & 1u) ? 0 : 1;
+                }
+            }
+        }
+        steps_exec += (unsigned long long)lam_max * n_valid;
+        __syncthreads();
+    }
+    if (tid == 0 && steps_exec) atomicAdd(&Q.ctr[1], steps_exec);
+}
+
+template <int K>
+static hipError_t launch_wide_profile_k(dim3 grid, size_t shmem, hipStream_t st, const WideProfileParams& Q) {
+    const void* fn = Q.net.wdesc ? (const void*)k_wide_profile<K, true> : (const void*)k_wide_profile<K, false>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return e;
+    void* args[] = {const_cast<WideProfileParams*>(&Q)};
+    return hipLaunchKernel(fn, grid, dim3(kWideThreads), args, shmem, st);
+}
+
+hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, const WideProfileParams& Q) {
+    switch (k) {
+        case 1: return launch_wide_profile_k<1>(grid, shmem, st, Q);
+        case 2: return launch_wide_profile_k<2>(grid, shmem, st, Q);
+        case 3: return launch_wide_profile_k<3>(grid, shmem, st, Q);
+        case 4: return launch_wide_profile_k<4>(grid, shmem, st, Q);
+        case 5: return launch_wide_profile_k<5>(grid, shmem, st, Q);
+        case 6: return launch_wide_profile_k<6>(grid, shmem, st, Q);
         default: return hipErrorInvalidValue;
     }
 }

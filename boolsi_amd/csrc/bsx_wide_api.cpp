@@ -14,6 +14,7 @@
 namespace bsx {
 
 hipError_t launch_wide(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& P);
+hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, const WideProfileParams& Q);
 hipError_t launch_wide_reduce_attract(const uint32_t* info, const uint64_t* keys, uint64_t m, uint32_t w64, WideSlot* table,
                                       uint64_t slots, unsigned long long* hdr, hipStream_t st);
 hipError_t launch_wide_reduce_drain(const WideSlot* table, uint64_t slots, WideAttrRec* out, uint64_t cap, unsigned long long* hdr,
@@ -330,6 +331,77 @@ int wide_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* 
         tmax = std::max(tmax, t_len[q]);
     }
     return wide_sim(h, first, n, tmax, offsets, t_len, out_offsets, words, out, nullptr, nullptr, stats);
+}
+
+// bsx_run_attractor_profile on the wide family (bsx_profile_api.cpp has checked every argument): one k_wide_profile
+// launch per BSX_PROFILE_CHUNK_WIDE attractors, all enqueued before the one wait.
+int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
+                     uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
+                     uint64_t sum_len, bsx_stats* stats) {
+    static_assert(BSX_PROFILE_CHUNK_WIDE % (32 * 64) == 0, "a chunk is whole groups for every L");
+    const double t_begin = now_ms();
+    WideHost& W = *h->wide;
+    if (W.rows / (kWideThreads / W.L) > kWideProfileRows)      // (before any device work, as every check of this call)
+        return fail(h, BSX_ERR_UNSUPPORTED, "wide profile: more rows per thread than the kernel holds");
+    DevBuf<uint64_t> d_keys, d_len, d_off, d_states;
+    DevBuf<uint32_t> d_on;
+    DevBuf<uint8_t> d_closed;
+    HIPCHK(h, d_keys.alloc(n * key_stride));
+    HIPCHK(h, hipMemcpy(d_keys.p, keys, n * key_stride * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, d_len.alloc(n));
+    HIPCHK(h, hipMemcpy(d_len.p, lengths, n * 8, hipMemcpyHostToDevice));
+    if (states) {
+        HIPCHK(h, d_off.alloc(n));
+        HIPCHK(h, hipMemcpy(d_off.p, state_offsets, n * 8, hipMemcpyHostToDevice));
+        HIPCHK(h, d_states.alloc(state_words));
+    }
+    if (on_counts) {
+        HIPCHK(h, d_on.alloc(n * W.n));
+        HIPCHK(h, hipMemsetAsync(d_on.p, 0, n * W.n * sizeof(uint32_t), h->stream));
+    }
+    if (closed) HIPCHK(h, d_closed.alloc(n));
+
+    WideProfileParams Q{};
+    WideParams& P = Q.net;
+    P.n_nodes = W.n; P.rows = W.rows; P.L = W.L;
+    P.lshift = (uint32_t)__builtin_ctz(W.L);
+    P.rows_ps = W.rows / (kWideThreads / W.L);
+    P.w64 = W.w64;
+    P.desc = W.d_desc.p; P.wdesc = W.wdesc.empty() ? nullptr : W.d_wdesc.p; P.wpreds = W.d_wpreds.p; P.wtt = W.d_wtt.p;
+    P.n_fslots = W.n_fslots;
+    Q.key_stride = key_stride;
+    Q.states = states ? d_states.p : nullptr;
+    Q.ctr = W.d_ctr.p;
+    const size_t shmem = (size_t)wide_profile_lds_words(W.rows, W.L, W.n_fslots) * 4;
+    const uint32_t G = 32 * W.L;
+    const uint32_t per_cu = std::max<uint32_t>(1, (uint32_t)((160 * 1024) / shmem));
+    uint32_t launches = 0;
+    HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    for (uint64_t at = 0; at < n; at += BSX_PROFILE_CHUNK_WIDE, ++launches) {
+        const uint64_t m = std::min<uint64_t>(BSX_PROFILE_CHUNK_WIDE, n - at);
+        Q.count = m;
+        Q.keys = d_keys.p + at * key_stride;
+        Q.lengths = d_len.p + at;
+        Q.state_offsets = states ? d_off.p + at : nullptr;
+        Q.on_counts = on_counts ? d_on.p + at * W.n : nullptr;
+        Q.closed = closed ? d_closed.p + at : nullptr;
+        const uint64_t groups = (m + G - 1) / G;
+        const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>(groups, (uint64_t)h->prop.multiProcessorCount * per_cu));
+        HIPCHK(h, launch_wide_profile((int)W.K, dim3((uint32_t)blocks), shmem, h->stream, Q));
+    }
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    unsigned long long ctr[4] = {0, 0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(ctr, W.d_ctr.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    if (on_counts) HIPCHK(h, hipMemcpy(on_counts, d_on.p, n * W.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (states && state_words) HIPCHK(h, hipMemcpy(states, d_states.p, state_words * 8, hipMemcpyDeviceToHost));
+    if (closed) HIPCHK(h, hipMemcpy(closed, d_closed.p, n, hipMemcpyDeviceToHost));
+    ctr[0] = sum_len;
+    put_stats(stats, n, ctr, ms, launches, t_begin);
+    return BSX_OK;
 }
 
 // target: first hit time per problem into t_hit (kWideNone = none)

@@ -153,6 +153,50 @@ class Engine:
             self.set_space(saved)
         return trajs[0]
 
+    def attractor_profile(self, keys, lengths, states=True, activity=True):
+        """
+        The attractors (key state code, length) of a whole table in one device call (bsx_run_attractor_profile):
+        every cycle is walked from its key under the origin problem's fixed nodes, without perturbations.
+        -> (on_counts, states, closed):
+           on_counts  (n, n_nodes) uint32, in how many of the cycle's states each node is on; None without `activity`
+           states     list of (length, W) uint64 arrays, first state = the key; None without `states`
+           closed     uint8 array, 1 iff f^length(key) == key
+        The problem space and the cycle-state cache of the engine are left as they are; `profile_stats` holds the
+        call's statistics afterwards.
+        """
+        W = self.net.n_words
+        n = len(keys)
+        ints = [int(k) for k in keys]               # Python ints: what merge_tables produces
+        if any(k < 0 or k >> (64 * W) for k in ints):
+            raise ValueError('a key does not fit the {} words of a state'.format(W))
+        key_words = np.zeros((n, W), np.uint64)
+        for w in range(W):
+            key_words[:, w] = [(k >> (64 * w)) & _M64 for k in ints]
+        lens = np.ascontiguousarray(lengths, np.uint64)
+        if lens.shape != (n,):
+            raise ValueError('one length per key')
+        on_counts = np.zeros((n, self.net.n_nodes), np.uint32) if activity else None
+        closed = np.zeros(n, np.uint8)
+        out = offsets = None
+        if states:
+            sizes = lens * np.uint64(W)
+            offsets = np.zeros(n, np.uint64)
+            if n > 1:
+                offsets[1:] = np.cumsum(sizes[:-1])
+            out = np.zeros(int(sizes.sum()), np.uint64)
+        st = Stats()
+        self._run_attractor_profile(ptr(key_words), W, ptr(lens), n, ptr(on_counts), ptr(out), ptr(offsets), ptr(closed), st)
+        self.profile_stats = st.as_dict()
+        listed = None
+        if states:
+            listed = [out[int(o):int(o) + int(l) * W].reshape(-1, W) for o, l in zip(offsets, lens)]
+        return on_counts, listed, closed
+
+    def _run_attractor_profile(self, keys, key_stride, lengths, n, on_counts, states, state_offsets, closed, stats):
+        """The ABI call itself; null pointers for the outputs that were not asked for."""
+        self._check(self._lib.bsx_run_attractor_profile(self._h, keys, key_stride, lengths, n, on_counts, states,
+                                                        state_offsets, closed, C.byref(stats)))
+
     def index(self, i):
         """python int problem index -> bsx_index (split at the initial-state digits)."""
         n_any = len(self.space.any_nodes)

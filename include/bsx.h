@@ -263,6 +263,29 @@ int  bsx_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* 
                           const uint64_t* t_len, uint64_t n, uint64_t* out,
                           const uint64_t* out_offsets, bsx_stats* stats);
 
+/* Profile of listed attractors, the whole table in one call (what the per-attractor bsx_run_trajectories loop of a
+ * host layer did): for each of n attractors given by (key state, length), walk the cycle from the key under the origin
+ * problem's fixed nodes, without perturbations (attract.py:22-25: the listed states start at the key state).
+ *   on_counts[q * n_nodes + i] = number of the cycle's `length` states in which node i is 1      (nullable)
+ *   states[state_offsets[q] + t * W + w], t = 0 .. length-1, state 0 = the key                    (nullable; then state_offsets too)
+ *   closed[q] = 1 iff f^length(key) == key                                                         (nullable)
+ * keys: n rows of key_stride words, the first W of each row used (W = words per state of the current network,
+ * 64-bit, little-endian as everywhere in this header).  Works for every supported network size.
+ * Checked before anything is launched: network and problem space are set (BSX_ERR_STATE otherwise, as in every
+ * bsx_run_* call); key_stride >= W; 1 <= length; no key bit at or above n_nodes; with `states`,
+ * state_offsets non-null and the ranges [offset, offset + length * W) disjoint -- the end of the last one is the size of
+ * `states` (BSX_ERR_INVALID otherwise); length below the family's step limit (2^30; on the wide family 2^24 lock steps,
+ * or BSX_WIDE_STEP_LIMIT: BSX_ERR_STEP_LIMIT otherwise).  A key that is not on a cycle of the stated length is not an
+ * error: closed[q] is 0 and the other outputs are the first `length` states from it.
+ * The handle's problem space and cycle-state cache are left alone.  stats: problems = n, state_steps = sum of the
+ * lengths.  The call makes one launch per BSX_PROFILE_CHUNK attractors (n <= 256 nodes) or per BSX_PROFILE_CHUNK_WIDE
+ * attractors (wide family) and waits for the device once, whatever n is. */
+#define BSX_PROFILE_CHUNK      (1ull << 22)
+#define BSX_PROFILE_CHUNK_WIDE (1ull << 18)
+int  bsx_run_attractor_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
+                               uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets,
+                               uint8_t* closed, bsx_stats* stats);
+
 /* Blocks until all work of the handle's stream is done (bench.py's timing fence). */
 int  bsx_synchronize(bsx_handle h);
 
