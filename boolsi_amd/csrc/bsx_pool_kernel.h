@@ -315,6 +315,8 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
     // is `s` a cached cycle state?  -> the entry's tag word (0 = no); `hfull` = the state's hash
     uint32_t hit_len = 0;                   // NW <= 2: the entry's length word comes with the probe's 16-byte read
     // (representative entries of a cube pass count only for the t = 0 probe: `reps`)
+    // NOT for the `P.leaf` branch of the lower build: it moves the mirror's occupied entries to the front, after which the
+    // mirror is a list and no hash table any more -- a lookup added there has to come before that, or walk the list.
     auto probe = [&](const uint32_t (&s)[NW], uint32_t& hfull, bool reps = false) -> uint32_t {
         const uint32_t ignore = reps ? 0u : kTagRep;
         hfull = hash_state<NW>(s);
@@ -432,6 +434,31 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
             uint32_t* const dep_lds = midtab + 64 * NW;
             for (uint32_t i = threadIdx.x; i < n_dep * 4u; i += blockDim.x) dep_lds[i] = reinterpret_cast<const uint32_t*>(L->dep)[i];
             __syncthreads();
+            // The mirror is walked here, never probed, and the walk visits every entry for every work item -- at a fill of a
+            // quarter or less most of them empty slots, each a full LDS round trip.  So the occupied entries move to the front
+            // once (state words and tag word: lamtab and keytab have the rest), 64 slots per wave and round, in place: an entry
+            // lands among the slots up to the end of its round, all of them read (this round, before the barrier, or earlier).
+            // Their order is that of the waves' arrival, and every result is a sum.  lc[1] counts them (free by now: everybody
+            // is past the barrier above, so past reading it for t0_lookup).
+            if (threadIdx.x == 0) lc[1] = 0;
+            for (uint32_t sl0 = 0; sl0 < P.cc.lds_slots; sl0 += blockDim.x) {
+                const uint32_t sl = sl0 + threadIdx.x;
+                uint32_t ew[NW + 1];
+#pragma unroll
+                for (int w = 0; w <= NW; ++w) ew[w] = sl < P.cc.lds_slots ? lc[kCacheHeaderWords + sl * S + w] : 0u;
+                __syncthreads();
+                const bool occ = (ew[NW] & kTagMask) != 0;
+                const uint64_t ob = __ballot(occ);
+                uint32_t at0 = 0;
+                if (lane == 0 && ob) at0 = atomicAdd((uint32_t*)(__attribute__((address_space(3))) uint32_t*)&lc[1], (uint32_t)__popcll(ob));
+                const uint32_t at = __builtin_amdgcn_readfirstlane(at0) + rank_below(ob);
+                if (occ) {
+#pragma unroll
+                    for (int w = 0; w <= NW; ++w) lc[kCacheHeaderWords + at * S + w] = ew[w];
+                }
+            }
+            __syncthreads();
+            const uint32_t n_occupied = __builtin_amdgcn_readfirstlane(lc[1]);
             // work item = (parent, part of its children): items [part * listed64, (part + 1) * listed64) are part `part` of all parents
             const unsigned long long listed = P.level_in->n_entries, listed64 = (listed + 63ull) & ~63ull;
             const uint32_t parts = leaf_parts(kb, listed, (uint64_t)gridDim.x * kPoolWaves);
@@ -468,10 +495,10 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
                 }
                 q.next += n;
                 uint32_t hits = 0;
-                for (uint32_t sl = 0; sl < P.cc.lds_slots; ++sl) {          // (uniform: every lane looks at the same entry)
+                for (uint32_t sl = 0; sl < n_occupied; ++sl) {              // (uniform: every lane looks at the same entry)
                     const uint32_t* e = cbase + sl * S;
                     const uint32_t tagw = __builtin_amdgcn_readfirstlane(e[NW]);
-                    if ((tagw & kTagMask) == 0) continue;
+                    if ((tagw & kTagMask) == 0) continue;                   // (none is left in front: one scalar compare, kept as a guard)
                     {
                         // A cycle state inside the block is the representative of its class either as a flagged entry of its own
                         // (its irrelevant bits cleared) or, if it has none set, as itself.  Is that class a child of this parent --
