@@ -23,10 +23,12 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 EXPORTS = (
     'bsx_create', 'bsx_destroy', 'bsx_last_error', 'bsx_status_string', 'bsx_device_info', 'bsx_network_info',
     'bsx_set_network', 'bsx_set_problem_space', 'bsx_run_attract', 'bsx_run_attract2', 'bsx_run_attract_wide', 'bsx_run_attract_fgraph', 'bsx_run_target',
-    'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_run_attractor_profile', 'bsx_synchronize',
+    'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_run_attractor_profile', 'bsx_run_node_correlations', 'bsx_synchronize',
     'bsx_comm_unique_id', 'bsx_comm_init', 'bsx_comm_allgather', 'bsx_comm_destroy',
 )
 COMM_ID_BYTES = 128
+CORR_CHUNK = 4096           # BSX_CORR_CHUNK: attractors per covariance partial of bsx_run_node_correlations
+CORR_MAX_CELLS = 1 << 31    # BSX_CORR_MAX_CELLS
 
 
 class EngineUnavailable(RuntimeError):
@@ -143,6 +145,7 @@ def load():
     lib.bsx_run_simulate.argtypes = [vp, C.POINTER(Index), u64, u64, vp, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_trajectories.argtypes = [vp, C.POINTER(Index), vp, vp, u64, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_attractor_profile.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, vp, C.POINTER(Stats)]
+    lib.bsx_run_node_correlations.argtypes = [vp, vp, u32, vp, vp, u64, vp, vp, vp, vp, C.POINTER(Stats)]
     lib.bsx_synchronize.argtypes = [vp]
     lib.bsx_comm_unique_id.argtypes = [vp, vp, u32]
     lib.bsx_comm_init.argtypes = [vp, vp, u32, C.c_int, C.c_int]

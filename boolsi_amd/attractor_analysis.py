@@ -1,7 +1,11 @@
 """
 Node correlations across attractors: frequency-weighted Spearman's rho and two-sided p-values
-(reference `boolsi/attractor_analysis.py:29-145`; SURVEY f-3).  Host-side numpy on at most a few
-thousand attractors; not on the GPU path.
+(reference `boolsi/attractor_analysis.py:29-145`; SURVEY f-3).
+
+Two paths to rho: host-side numpy (ranks by one sort per node column, then np.cov), as the reference does it, for
+small tables; and for tables of DEVICE_CORRELATION_CELLS cells or more one device call (Engine.node_correlations,
+DESIGN.md "Node correlations") that returns S = sum_q f_q d2_qa d2_qb over exact centred integer ranks.  Both hand
+their matrix to correlation_statistics(), which forms rho, t and the p-values.
 """
 import logging
 
@@ -22,16 +26,27 @@ def weighted_ranks(values, weights):
     return ranks
 
 
-def weighted_pearson(data, weights):
-    """Pearson r between columns of `data` with integer row weights, and t-test p-values."""
-    dof = weights.sum() - 2
-    cov = np.cov(data.T, fweights=weights)
-    var = cov.diagonal()
+# Tables of at least this many cells (attractors x nodes) take the device path when an engine is at hand.  Measured
+# (tools/bench_correlations.py, profiles/node_correlations.json): every device run beats every host
+# run from 2^12 cells up at 64 and at 1024 nodes, so the constant is the floor -- below it nothing is gained, and every
+# published example stays on the host path, byte for byte.
+DEVICE_CORRELATION_CELLS = 1 << 12
+
+
+def correlation_statistics(cross, dof):
+    """rho and two-sided t-test p-values from a matrix proportional to the covariance of the ranks (np.cov's, or the
+    device's S: the scale cancels in rho).  A zero on the diagonal (a constant node) makes its pairs NaN."""
+    var = cross.diagonal()
     with np.errstate(invalid='ignore', divide='ignore'):
-        r = cov / np.sqrt(np.multiply.outer(var, var))
+        r = cross / np.sqrt(np.multiply.outer(var, var))
         t = r / np.sqrt((1 - r * r) / dof)
         p = 2 * stats.t.sf(np.abs(t), dof)
     return r, p
+
+
+def weighted_pearson(data, weights):
+    """Pearson r between columns of `data` with integer row weights, and t-test p-values."""
+    return correlation_statistics(np.cov(data.T, fweights=weights), weights.sum() - 2)
 
 
 def compute_frequency_spearmanrho(data, frequencies):
@@ -39,16 +54,49 @@ def compute_frequency_spearmanrho(data, frequencies):
     return weighted_pearson(ranks, frequencies)
 
 
-def find_node_correlations(attractors):
+def uses_device(n_attractors, n_nodes, engine=None, device=None):
+    """Which path find_node_correlations takes: `device` True / False forces one (tests, A/B runs); None applies the
+    size rule, and without an engine there is only the host path."""
+    if device is not None:
+        return bool(device)
+    return engine is not None and n_attractors * n_nodes >= DEVICE_CORRELATION_CELLS
+
+
+def find_node_correlations(attractors, engine=None, device=None):
     """attractors: list of AggregatedAttractor with .frequency and .activity or .states -> (Rho, P) or None.
     An observation is a node's mean state over the attractor: .activity (on-counts / length, from the device) where it
-    is there, else the mean over .states -- the same float64, an exact integer sum divided by the length."""
+    is there, else the mean over .states -- the same float64, an exact integer sum divided by the length.
+    With an `engine` (its problem set, as attract_master leaves it) large tables go through one device call that needs
+    only key, length and frequency of every attractor (uses_device); a table the device call refuses for its size
+    (total frequency of 2^62 or more, more than 2^31 cells) takes the host path."""
+    log = logging.getLogger()
     total = sum(a.frequency for a in attractors)
     if len(attractors) == 1 or total <= 2:
-        logging.getLogger().info('Not enough attractors to infer node correlations.')
+        log.info('Not enough attractors to infer node correlations.')
         return None
+    if engine is not None and uses_device(len(attractors), engine.net.n_nodes, engine, device):
+        from ._lib import EngineError, ERR_RANGE_TOO_LARGE, ERR_UNSUPPORTED
+        log.info('Computing node correlations on the device ({} attractors x {} nodes)...'.format(
+            len(attractors), engine.net.n_nodes))
+        try:
+            S, _, _, closed = engine.node_correlations([a.key for a in attractors], [a.length for a in attractors],
+                                                       [a.frequency for a in attractors])
+        except EngineError as e:
+            if e.status not in (ERR_RANGE_TOO_LARGE, ERR_UNSUPPORTED):
+                raise
+            log.info('The device call does not take this table ({}); computing node correlations on the host.'.format(e))
+        else:
+            for a, c in zip(attractors, closed):
+                if not c:
+                    raise RuntimeError('attractor {} does not return to its key state after {} steps'.format(a.key, a.length))
+            return correlation_statistics(S, total - 2)
+    elif device:
+        raise ValueError('the device path needs an engine')
+    if engine is not None and any(getattr(a, 'activity', None) is None and a.states is None for a in attractors):
+        from .attract import profile_attractors
+        profile_attractors(engine, attractors, with_states=False, with_activity=True)
     observations = np.array([a.activity if getattr(a, 'activity', None) is not None else
                              np.mean(np.array(a.states, dtype=float), axis=0) for a in attractors])
     frequencies = np.array([a.frequency for a in attractors])
-    logging.getLogger().info('Computing node correlations...')
+    log.info('Computing node correlations...')
     return compute_frequency_spearmanrho(observations, frequencies)

@@ -172,8 +172,8 @@ def simulate(**kw):
               help='p-value threshold for statistical significance of node correlations. Defaults to 0.05.')
 def attract(**kw):
     def body(run):
-        from .attract import attract_master
-        from .attractor_analysis import find_node_correlations
+        from .attract import attract_master, profile_attractors
+        from .attractor_analysis import find_node_correlations, uses_device
         from .output import output_attractors, output_node_correlations
         max_t = kw['max_simulation_time'] or inf
         max_len = kw['max_attractor_length'] or inf
@@ -181,11 +181,14 @@ def attract(**kw):
         if kw['no_node_correlations'] and kw['no_attractor_output']:
             logging.getLogger().info("Cannot proceed, both attractors' and node correlations' output is disabled.")
             return
+        # node activity comes along with the states; without them (-x) it is asked for below, and only if the
+        # correlations take the host path: the device path needs no per-attractor data on the host
+        engine = run.open_engine()
         attractors, n_none, total_frequency, stats = attract_master(
-            run.open_engine(), cfg['origin simulation problem'], cfg['simulation problem variations'],
+            engine, cfg['origin simulation problem'], cfg['simulation problem variations'],
             cfg['incoming node lists'], cfg['truth tables'], max_t, max_len,
-            cfg['total combination count'], comm=run.comm,
-            with_states=not kw['no_attractor_output'], with_activity=not kw['no_node_correlations'])
+            cfg['total combination count'], comm=run.comm, with_states=not kw['no_attractor_output'],
+            with_activity=not kw['no_node_correlations'] and not kw['no_attractor_output'])
         if run.comm.rank != 0:
             return
         logging.getLogger().info(
@@ -194,7 +197,9 @@ def attract(**kw):
         if not attractors:
             return
         if not kw['no_node_correlations']:
-            correlations = find_node_correlations(attractors)
+            if kw['no_attractor_output'] and not uses_device(len(attractors), len(cfg['node names']), engine):
+                profile_attractors(engine, attractors, with_states=False, with_activity=True)
+            correlations = find_node_correlations(attractors, engine=engine)
             if correlations:
                 output_node_correlations(correlations[0], correlations[1], kw['p_value'], cfg['node names'], run.out)
         if not kw['no_attractor_output']:

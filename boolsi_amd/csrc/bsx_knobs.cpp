@@ -44,6 +44,7 @@ Knobs Knobs::from_env() {
     if (const char* e = std::getenv("BSX_WIDE_CHUNK")) if (e[0]) { k.wide_chunk_set = true; k.wide_chunk = std::strtoull(e, nullptr, 10); }
     k.wide_step_limit = kWideStepLimit;
     if (const char* e = std::getenv("BSX_WIDE_STEP_LIMIT")) k.wide_step_limit = std::max(16u, std::min(kWideStepLimit, (uint32_t)std::atoi(e)));
+    if (const char* e = std::getenv("BSX_CORR_BATCH_CELLS")) k.corr_batch_cells = std::strtoull(e, nullptr, 10);
     return k;
 }
 

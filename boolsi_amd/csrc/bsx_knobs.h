@@ -36,6 +36,7 @@ struct Knobs {
     bool wide_chunk_set = false;    // BSX_WIDE_CHUNK (not empty): problems per k_wide launch of a chunked run,
     uint64_t wide_chunk = 0;        // ... clamped where it is used (the lower bound depends on the network)
     uint32_t wide_step_limit = 0;   // BSX_WIDE_STEP_LIMIT: 16 .. kWideStepLimit (default: kWideStepLimit)
+    uint64_t corr_batch_cells = 0;  // BSX_CORR_BATCH_CELLS: cells (columns x attractors) per sort batch of the node correlations (0 = not set)
 
     static Knobs from_env();
 };

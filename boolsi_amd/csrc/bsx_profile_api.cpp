@@ -19,12 +19,19 @@ namespace {
 constexpr uint64_t kProfileChunk = 1ull << 22;
 static_assert(kProfileChunk == BSX_PROFILE_CHUNK, "the header states the chunk size");
 
+}  // namespace
+
+namespace bsx {
+
+// keep_on: the on-counts are counted whether or not the caller wants them on the host, and stay in *keep_on
 int profile_lanes(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
                   uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words,
-                  uint8_t* closed, uint64_t sum_len, bsx_stats* stats, double t_begin) {
+                  uint8_t* closed, uint64_t sum_len, bsx_stats* stats, double t_begin, DevBuf<uint32_t>* keep_on) {
     const uint32_t W = h->w64, n_nodes = h->n_nodes;
     DevBuf<uint64_t> d_keys, d_len, d_off, d_states;
-    DevBuf<uint32_t> d_on;
+    DevBuf<uint32_t> d_on_here;
+    DevBuf<uint32_t>& d_on = keep_on ? *keep_on : d_on_here;
+    const bool count_on = on_counts || keep_on;
     DevBuf<uint8_t> d_closed;
     HIPCHK(h, d_keys.alloc(n * key_stride));
     HIPCHK(h, hipMemcpy(d_keys.p, keys, n * key_stride * 8, hipMemcpyHostToDevice));
@@ -35,7 +42,7 @@ int profile_lanes(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const
         HIPCHK(h, hipMemcpy(d_off.p, state_offsets, n * 8, hipMemcpyHostToDevice));
         HIPCHK(h, d_states.alloc(state_words));
     }
-    if (on_counts) {
+    if (count_on) {
         HIPCHK(h, d_on.alloc(n * n_nodes));
         HIPCHK(h, hipMemsetAsync(d_on.p, 0, n * n_nodes * sizeof(uint32_t), h->stream));
     }
@@ -58,7 +65,7 @@ int profile_lanes(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const
         P.keys = d_keys.p + at * key_stride;
         P.lengths = d_len.p + at;
         P.state_offsets = states ? d_off.p + at : nullptr;
-        P.on_counts = on_counts ? d_on.p + at * n_nodes : nullptr;
+        P.on_counts = count_on ? d_on.p + at * n_nodes : nullptr;
         P.closed = closed ? d_closed.p + at : nullptr;
         const uint64_t block = (uint64_t)profile_block((int)h->net.nw);
         const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * 4, (m + block - 1) / block));
@@ -84,7 +91,54 @@ int profile_lanes(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const
     return BSX_OK;
 }
 
-}  // namespace
+// Everything bsx_run_attractor_profile checks before it launches (include/bsx.h); `who` names the entry point in the
+// error text.  n > 0.  -> sum of the lengths, size of `states` in words.
+int profile_check_args(bsx_handle h, const char* who, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths,
+                       uint64_t n, const uint64_t* states, const uint64_t* state_offsets, uint64_t* sum_len_out,
+                       uint64_t* state_words_out) {
+    const std::string name(who);
+    if (!keys || !lengths) return fail(h, BSX_ERR_INVALID, name + ": keys or lengths is null");
+    if (states && !state_offsets) return fail(h, BSX_ERR_INVALID, name + ": states without state_offsets");
+    const uint32_t W = h->w64, n_nodes = h->n_nodes;
+    if (key_stride < W) return fail(h, BSX_ERR_INVALID, name + ": key_stride is below the words per state");
+    if (n > (1ull << 32)) return fail(h, BSX_ERR_INVALID, "at most 2^32 attractors per call");
+    // lengths: 1 <= length, and no walk beyond the family's step limit (the wide family counts lock steps of a group,
+    // which makes as many as its longest walk; BSX_WIDE_STEP_LIMIT lowers that limit)
+    const uint64_t limit = h->wide ? std::min<uint64_t>(kStepLimit, h->knobs.wide_step_limit) : kStepLimit;
+    uint64_t sum_len = 0;
+    bool too_long = false;
+    for (uint64_t q = 0; q < n; ++q) {
+        if (lengths[q] == 0) return fail(h, BSX_ERR_INVALID, name + ": an attractor of length 0");
+        too_long = too_long || lengths[q] >= limit;
+        if (!too_long) sum_len += lengths[q];
+    }
+    if (too_long) return fail(h, BSX_ERR_STEP_LIMIT, name + ": a walk would exceed the internal step limit");
+    // keys: no bit at or above n_nodes in the words the kernels read
+    if (n_nodes & 63u) {
+        const uint64_t above = ~0ull << (n_nodes & 63u);
+        for (uint64_t q = 0; q < n; ++q)
+            if (keys[q * key_stride + (W - 1)] & above)
+                return fail(h, BSX_ERR_INVALID, name + ": a key has bits at or above n_nodes");
+    }
+    // states: the ranges [offset, offset + length * W) must not overlap; their end is the size of the output
+    uint64_t state_words = 0;
+    if (states) {
+        std::vector<uint64_t> order(n);
+        std::iota(order.begin(), order.end(), 0ull);
+        std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return state_offsets[a] < state_offsets[b]; });
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t off = state_offsets[order[i]], need = lengths[order[i]] * W;     // (< 2^30 * 16)
+            if (off < state_words) return fail(h, BSX_ERR_INVALID, name + ": state ranges overlap");
+            if (off > (1ull << 56)) return fail(h, BSX_ERR_INVALID, name + ": state offset out of range");
+            state_words = off + need;
+        }
+    }
+    *sum_len_out = sum_len;
+    *state_words_out = state_words;
+    return BSX_OK;
+}
+
+}  // namespace bsx
 
 extern "C" int bsx_run_attractor_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths,
                                          uint64_t n, uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets,
@@ -95,46 +149,14 @@ extern "C" int bsx_run_attractor_profile(bsx_handle h, const uint64_t* keys, uin
     const double t_begin = now_ms();
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n == 0) return BSX_OK;
-    if (!keys || !lengths) return fail(h, BSX_ERR_INVALID, "bsx_run_attractor_profile: keys or lengths is null");
-    if (states && !state_offsets) return fail(h, BSX_ERR_INVALID, "bsx_run_attractor_profile: states without state_offsets");
-    const uint32_t W = h->w64, n_nodes = h->n_nodes;
-    if (key_stride < W) return fail(h, BSX_ERR_INVALID, "bsx_run_attractor_profile: key_stride is below the words per state");
-    if (n > (1ull << 32)) return fail(h, BSX_ERR_INVALID, "at most 2^32 attractors per call");
-    // lengths: 1 <= length, and no walk beyond the family's step limit (the wide family counts lock steps of a group,
-    // which makes as many as its longest walk; BSX_WIDE_STEP_LIMIT lowers that limit)
-    const uint64_t limit = h->wide ? std::min<uint64_t>(kStepLimit, h->knobs.wide_step_limit) : kStepLimit;
-    uint64_t sum_len = 0;
-    bool too_long = false;
-    for (uint64_t q = 0; q < n; ++q) {
-        if (lengths[q] == 0) return fail(h, BSX_ERR_INVALID, "bsx_run_attractor_profile: an attractor of length 0");
-        too_long = too_long || lengths[q] >= limit;
-        if (!too_long) sum_len += lengths[q];
-    }
-    if (too_long) return fail(h, BSX_ERR_STEP_LIMIT, "bsx_run_attractor_profile: a walk would exceed the internal step limit");
-    // keys: no bit at or above n_nodes in the words the kernels read
-    if (n_nodes & 63u) {
-        const uint64_t above = ~0ull << (n_nodes & 63u);
-        for (uint64_t q = 0; q < n; ++q)
-            if (keys[q * key_stride + (W - 1)] & above)
-                return fail(h, BSX_ERR_INVALID, "bsx_run_attractor_profile: a key has bits at or above n_nodes");
-    }
-    // states: the ranges [offset, offset + length * W) must not overlap; their end is the size of the output
-    uint64_t state_words = 0;
-    if (states) {
-        std::vector<uint64_t> order(n);
-        std::iota(order.begin(), order.end(), 0ull);
-        std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return state_offsets[a] < state_offsets[b]; });
-        for (uint64_t i = 0; i < n; ++i) {
-            const uint64_t off = state_offsets[order[i]], need = lengths[order[i]] * W;     // (< 2^30 * 16)
-            if (off < state_words) return fail(h, BSX_ERR_INVALID, "bsx_run_attractor_profile: state ranges overlap");
-            if (off > (1ull << 56)) return fail(h, BSX_ERR_INVALID, "bsx_run_attractor_profile: state offset out of range");
-            state_words = off + need;
-        }
-    }
+    uint64_t sum_len = 0, state_words = 0;
+    if (int rc = profile_check_args(h, "bsx_run_attractor_profile", keys, key_stride, lengths, n, states, state_offsets, &sum_len,
+                                    &state_words))
+        return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if (h->wide)
         return wide_run_profile(h, keys, key_stride, lengths, n, on_counts, states, state_offsets, state_words, closed, sum_len,
-                                stats);
+                                stats, nullptr);
     return profile_lanes(h, keys, key_stride, lengths, n, on_counts, states, state_offsets, state_words, closed, sum_len, stats,
-                         t_begin);
+                         t_begin, nullptr);
 }

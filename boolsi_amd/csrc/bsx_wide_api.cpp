@@ -337,14 +337,16 @@ int wide_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* 
 // launch per BSX_PROFILE_CHUNK_WIDE attractors, all enqueued before the one wait.
 int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
                      uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
-                     uint64_t sum_len, bsx_stats* stats) {
+                     uint64_t sum_len, bsx_stats* stats, DevBuf<uint32_t>* keep_on) {
     static_assert(BSX_PROFILE_CHUNK_WIDE % (32 * 64) == 0, "a chunk is whole groups for every L");
     const double t_begin = now_ms();
     WideHost& W = *h->wide;
     if (W.rows / (kWideThreads / W.L) > kWideProfileRows)      // (before any device work, as every check of this call)
         return fail(h, BSX_ERR_UNSUPPORTED, "wide profile: more rows per thread than the kernel holds");
     DevBuf<uint64_t> d_keys, d_len, d_off, d_states;
-    DevBuf<uint32_t> d_on;
+    DevBuf<uint32_t> d_on_here;
+    DevBuf<uint32_t>& d_on = keep_on ? *keep_on : d_on_here;   // (keep_on: counted in any case, and left there)
+    const bool count_on = on_counts || keep_on;
     DevBuf<uint8_t> d_closed;
     HIPCHK(h, d_keys.alloc(n * key_stride));
     HIPCHK(h, hipMemcpy(d_keys.p, keys, n * key_stride * 8, hipMemcpyHostToDevice));
@@ -355,7 +357,7 @@ int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, co
         HIPCHK(h, hipMemcpy(d_off.p, state_offsets, n * 8, hipMemcpyHostToDevice));
         HIPCHK(h, d_states.alloc(state_words));
     }
-    if (on_counts) {
+    if (count_on) {
         HIPCHK(h, d_on.alloc(n * W.n));
         HIPCHK(h, hipMemsetAsync(d_on.p, 0, n * W.n * sizeof(uint32_t), h->stream));
     }
@@ -384,7 +386,7 @@ int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, co
         Q.keys = d_keys.p + at * key_stride;
         Q.lengths = d_len.p + at;
         Q.state_offsets = states ? d_off.p + at : nullptr;
-        Q.on_counts = on_counts ? d_on.p + at * W.n : nullptr;
+        Q.on_counts = count_on ? d_on.p + at * W.n : nullptr;
         Q.closed = closed ? d_closed.p + at : nullptr;
         const uint64_t groups = (m + G - 1) / G;
         const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>(groups, (uint64_t)h->prop.multiProcessorCount * per_cu));

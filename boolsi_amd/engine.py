@@ -197,6 +197,51 @@ class Engine:
         self._check(self._lib.bsx_run_attractor_profile(self._h, keys, key_stride, lengths, n, on_counts, states,
                                                         state_offsets, closed, C.byref(stats)))
 
+    def node_correlations(self, keys, lengths, frequencies, ranks=False, activity=False):
+        """
+        The matrix behind the frequency-weighted Spearman correlations of a whole attractor table in one device call
+        (bsx_run_node_correlations): attractor q = (key state code, length), occurring frequencies[q] times.
+        -> (S, ranks, on_counts, closed):
+           S          (n_nodes, n_nodes) float64, S[a][b] = sum_q f_q d2[q][a] d2[q][b] with d2 twice the centred average
+                      rank; rho = S[a][b] / sqrt(S[a][a] S[b][b]); symmetric and reproducible bit for bit
+           ranks      (n, n_nodes) float64 average weighted ranks; None without `ranks`
+           on_counts  (n, n_nodes) uint32 as attractor_profile; None without `activity`
+           closed     uint8 array, 1 iff f^length(key) == key
+        An EngineError with status ERR_RANGE_TOO_LARGE (total frequency of 2^62 or more) or ERR_UNSUPPORTED (more than
+        2^31 cells) means the table is for the host path.  `corr_stats` holds the call's statistics afterwards.
+        """
+        W, n_nodes = self.net.n_words, self.net.n_nodes
+        n = len(keys)
+        ints = [int(k) for k in keys]
+        if any(k < 0 or k >> (64 * W) for k in ints):
+            raise ValueError('a key does not fit the {} words of a state'.format(W))
+        key_words = np.zeros((n, W), np.uint64)
+        for w in range(W):
+            key_words[:, w] = [(k >> (64 * w)) & _M64 for k in ints]
+        lens = np.ascontiguousarray(lengths, np.uint64)
+        freqs = [int(f) for f in frequencies]
+        if lens.shape != (n,) or len(freqs) != n:
+            raise ValueError('one length and one frequency per key')
+        if any(f < 0 or f >> 128 for f in freqs):
+            raise ValueError('a frequency does not fit 128 bits')
+        freq_words = np.zeros((n, 2), np.uint64)
+        freq_words[:, 0] = [f & _M64 for f in freqs]
+        freq_words[:, 1] = [f >> 64 for f in freqs]
+        s_matrix = np.zeros((n_nodes, n_nodes), np.float64)
+        rank_out = np.zeros((n, n_nodes), np.float64) if ranks else None
+        on_counts = np.zeros((n, n_nodes), np.uint32) if activity else None
+        closed = np.zeros(n, np.uint8)
+        st = Stats()
+        self._run_node_correlations(ptr(key_words), W, ptr(lens), ptr(freq_words), n, ptr(s_matrix), ptr(rank_out),
+                                    ptr(on_counts), ptr(closed), st)
+        self.corr_stats = st.as_dict()
+        return s_matrix, rank_out, on_counts, closed
+
+    def _run_node_correlations(self, keys, key_stride, lengths, frequencies, n, s_matrix, ranks, on_counts, closed, stats):
+        """The ABI call itself; null pointers for the outputs that were not asked for."""
+        self._check(self._lib.bsx_run_node_correlations(self._h, keys, key_stride, lengths, frequencies, n, s_matrix, ranks,
+                                                        on_counts, closed, C.byref(stats)))
+
     def index(self, i):
         """python int problem index -> bsx_index (split at the initial-state digits)."""
         n_any = len(self.space.any_nodes)

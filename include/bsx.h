@@ -286,6 +286,35 @@ int  bsx_run_attractor_profile(bsx_handle h, const uint64_t* keys, uint32_t key_
                                uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets,
                                uint8_t* closed, bsx_stats* stats);
 
+/* Node correlations of a whole attractor table: the matrix behind the frequency-weighted Spearman correlations of
+ * attractor_analysis.find_node_correlations, in one call.  keys / key_stride / lengths / n, on_counts and closed are
+ * those of bsx_run_attractor_profile; attractor q occurs frequencies[q] times.
+ *   observation of node i in attractor q = on_count / length (IEEE double division of the two integers);
+ *   per node column, rank2 = 2 W_less + W_equal + 1 (twice the average rank; W_less / W_equal = total frequency of the
+ *   attractors with a smaller / an equal observation, q included) as an exact 64-bit integer; its weighted mean is
+ *   T + 1 (T = sum of the frequencies), so d2 = rank2 - (T + 1) is an exact signed integer, converted to double once;
+ *   s_matrix[a * n_nodes + b] = sum over q of frequencies[q] * d2[q][a] * d2[q][b]                     (required)
+ *   ranks[q * n_nodes + i]    = rank2 / 2, the average weighted rank of attractor q in node i's column  (nullable)
+ * rho_ab = S_ab / sqrt(S_aa S_bb) (the scale factors cancel); a node that is constant over the table has S_aa == +0
+ * exactly.  s_matrix is symmetric bit for bit and the same bit for bit from run to run (upper-triangle tiles, no
+ * floating-point atomics, partial sums of BSX_CORR_CHUNK attractors each added in chunk order).
+ * Checked before anything is launched: everything bsx_run_attractor_profile checks; frequencies and s_matrix non-null,
+ * every frequency at least 1 (BSX_ERR_INVALID); every frequency's high word 0 and T < 2^62 (BSX_ERR_RANGE_TOO_LARGE);
+ * n * n_nodes <= BSX_CORR_MAX_CELLS (BSX_ERR_UNSUPPORTED).  n == 0 is BSX_OK with nothing written; n == 1 gives an
+ * all-zero matrix.  Works for every supported network size; problem space, cycle-state cache and its mirror image are
+ * left alone.  stats: those of the profile part, kernel_ms and kernel_launches with the correlation kernels added
+ * (each column batch's sort counts as one launch).
+ * Device memory, from the allocation sizes: 12 bytes per cell (on-counts, d2), 8 more with `ranks`, 32 bytes per cell
+ * of one column batch (2^24 cells, or one column if that is more) plus the sort's own workspace of about 12 more,
+ * 2 KiB per upper-triangle tile pair and chunk, 16 bytes per attractor.  At BSX_CORR_MAX_CELLS cells that is about
+ * 43 GiB for 1024 nodes x 2^21 attractors with ranks (24 + 16 + 0.7 + 2 GiB of partials); the extreme of one node x
+ * 2^31 attractors, whose only column is one batch, needs about 160 GiB. */
+#define BSX_CORR_CHUNK     4096u
+#define BSX_CORR_MAX_CELLS (1ull << 31)
+int  bsx_run_node_correlations(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths,
+                               const bsx_u128* frequencies, uint64_t n, double* s_matrix, double* ranks,
+                               uint32_t* on_counts, uint8_t* closed, bsx_stats* stats);
+
 /* Blocks until all work of the handle's stream is done (bench.py's timing fence). */
 int  bsx_synchronize(bsx_handle h);
 

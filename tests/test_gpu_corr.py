@@ -1,0 +1,441 @@
+"""
+bsx_run_node_correlations / Engine.node_correlations: the matrix S behind the frequency-weighted Spearman correlations
+of a whole attractor table in one device call, against the exact integer reference of tests/corr_ref.py.
+
+What every comparison checks (check_table): ranks by exact equality; on_counts equal to Engine.attractor_profile's;
+the NaN pattern of rho; |S_dev - S_exact| <= (n + 16) 2^-52 sqrt(S_aa S_bb) (summation bound with Cauchy-Schwarz, any
+order; the 16 covers the operand roundings); |rho_dev - rho_exact| <= 1e-9, the project's tolerance for float
+statistics; S == S.T bitwise; two calls bitwise equal; positive diagonal for non-constant nodes.  Each case asserts
+from the reference alone that it is not vacuous.
+
+A note on ties: observations are float64 quotients on_count / length.  1/2, 2/4 and 105/210 are one double and tie; so
+are 1/3 and 341/1023 (the same rational, and IEEE division is correctly rounded) -- tests/test_corr_ref.py pins both.
+
+The cases for networks of up to 256 nodes are plain functions of an engine; one of them runs once more in a fresh child
+process with BSX_WIDE=1, where the same network is lowered to the wide-state family.
+"""
+import csv
+import ctypes
+import functools
+import logging
+import os
+import random
+import subprocess
+import sys
+from math import gcd
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == '__main__':
+    sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+
+import corr_ref
+from boolsi_amd import _lib, attractor_analysis, synth
+from boolsi_amd.attract import AggregatedAttractor, attract_master
+from boolsi_amd.attractor_analysis import find_node_correlations
+from boolsi_amd.compile import compile_problem, words_to_code
+from boolsi_amd.constants import Mode
+from boolsi_amd.engine import Engine, EngineError
+from boolsi_amd.input import parse_input_text
+
+pytestmark = pytest.mark.gpu
+ERR_INVALID, ERR_UNSUPPORTED, ERR_STATE, ERR_RANGE_TOO_LARGE = -1, -4, -7, -9
+CHUNK = _lib.CORR_CHUNK
+GOLDEN = os.path.join(ROOT, 'tests', 'golden')
+
+
+# ---- networks -----------------------------------------------------------------------------------------------------------
+
+def yaml_of(preds, masks, init):
+    n = len(preds)
+    out = ['nodes:'] + ['    - {}'.format(synth.node_name(i)) for i in range(n)] + ['', 'update rules:']
+    out += ['    {}: {}'.format(synth.node_name(i), synth.rule_text(preds[i], masks[i])) for i in range(n)]
+    out += ['', 'initial state:'] + ['    {}: {}'.format(synth.node_name(i), init[i]) for i in range(n)]
+    return '\n'.join(out) + '\n'
+
+
+@functools.lru_cache(maxsize=None)
+def compiled(text):
+    cfg = parse_input_text(text, float('inf'), Mode.ATTRACT)
+    net, space = compile_problem(cfg)
+    return cfg, net, space
+
+
+def identity_text(n, n_any=8):
+    """every node keeps its state: every state is a fixed point, its on-counts are its bits"""
+    return yaml_of([[i] for i in range(n)], [0b10] * n, ['any' if i < n_any else '0' for i in range(n)])
+
+
+RINGS = (2, 3, 5, 7)
+
+
+def rings_text():
+    """disjoint rotation rings of 2, 3, 5 and 7 nodes: node <- its predecessor in the ring"""
+    preds, at = [], 0
+    for size in RINGS:
+        preds += [[at + (j - 1) % size] for j in range(size)]
+        at += size
+    return yaml_of(preds, [0b10] * at, ['any'] * at)
+
+
+def lfsr_text():
+    """6 identity nodes and a 10-node Fibonacci LFSR (x^10 + x^7 + 1, period 1023), as MIXED of test_gpu_profile.py"""
+    n, nodes, tap = 16, list(range(6, 16)), 7
+    preds, masks = [[i] for i in range(n)], [0b10] * n
+    a, b = sorted((nodes[-1], nodes[tap - 1]))
+    preds[nodes[0]], masks[nodes[0]] = [a, b], 0b0110
+    for i in range(1, len(nodes)):
+        preds[nodes[i]] = [nodes[i - 1]]
+    return yaml_of(preds, masks, ['any'] * n)
+
+
+# ---- tables: (text of the network, keys, lengths) -------------------------------------------------------------------------
+
+def identity_keys(n_nodes, count, seed, constant_node=None):
+    rng = random.Random(seed)
+    keys = set()
+    while len(keys) < count:
+        k = rng.getrandbits(n_nodes)
+        if constant_node is not None:
+            k &= ~(1 << constant_node)
+        keys.add(k)
+        if n_nodes <= 3 and len(keys) == 1 << (n_nodes - (constant_node is not None)):
+            break
+    return sorted(keys, key=lambda k: (k * 0x9E3779B1) & 0xFFFFFFFF)       # (not in key order)
+
+
+def rings_table():
+    """54 attractors: per ring one of three fillings; length = lcm of the periods.  Plus the 2-cycle of ring 2 stated with
+    length 4 (it closes: on-count 2 of 4) and with its true length 2."""
+    fillings = {2: ('00', '10'), 3: ('000', '100', '110'), 5: ('00000', '10000', '11000'), 7: ('0000000', '1000000', '1010000')}
+    keys, lengths = [], []
+
+    def walk(chosen, at, key, length):
+        if len(chosen) == len(RINGS):
+            keys.append(key)
+            lengths.append(length)
+            return
+        size = RINGS[len(chosen)]
+        for text in fillings[size]:
+            bits = sum(1 << (at + j) for j, ch in enumerate(text) if ch == '1')
+            period = size if '1' in text else 1
+            walk(chosen + [text], at + size, key | bits, length * period // gcd(length, period))
+    walk([], 0, 0, 1)
+    keys += [0b01, 0b10]
+    lengths += [4, 2]
+    return keys, lengths
+
+
+def lfsr_table():
+    """every identity assignment with the LFSR at rest (fixed points), the first 40 with it on its cycle: an unbalanced
+    design, so that identity and LFSR nodes correlate"""
+    keys, lengths = [], []
+    for x in range(64):
+        keys += [x | (1 << 6), x] if x < 40 else [x]
+        lengths += [1023, 1] if x < 40 else [1]
+    return keys, lengths
+
+
+def frequencies(kind, n, seed=7):
+    rng = random.Random(seed)
+    if kind == 'ones':
+        return [1] * n
+    if kind == 'mixed':
+        return [1 << rng.randint(0, 40) if rng.getrandbits(1) else rng.randint(1, 1 << 40) for _ in range(n)]
+    assert kind == 'top'                        # T = 2^62 - 1 exactly
+    top = (1 << 62) - 1
+    f = [top // n] * n
+    f[-1] += top - sum(f)
+    return f
+
+
+# ---- the comparison -------------------------------------------------------------------------------------------------------
+
+def check_table(eng, text, keys, lengths, freq, expect):
+    """expect: set of 'nan' (a constant node), 'ties', 'lengths' (at least two), 'rho' (a pair with 0 < |rho| < 1)"""
+    _, net, space = compiled(text)
+    eng.set_problem(net, space)
+    n, m = len(keys), net.n_nodes
+    on_profile, _, closed_profile = eng.attractor_profile(keys, lengths, states=False)
+    assert closed_profile.tolist() == [1] * n
+    ref = corr_ref.reference(on_profile, lengths, freq)
+    rho_ref = ref['rho']
+    if 'nan' in expect:
+        assert np.isnan(rho_ref).any() and not np.isnan(rho_ref).all()
+    if 'rho' in expect:
+        finite = np.abs(rho_ref[~np.isnan(rho_ref)])
+        assert ((finite > 0) & (finite < 1)).any()
+    if 'ties' in expect:
+        assert any(len(set(ref['rank2'][:, i].tolist())) < n for i in range(m))
+    if 'lengths' in expect:
+        assert len(set(lengths)) >= 2
+
+    S, ranks, on, closed = eng.node_correlations(keys, lengths, freq, ranks=True, activity=True)
+    assert eng.corr_stats['problems'] == n and eng.corr_stats['state_steps'] == sum(lengths)
+    assert closed.tolist() == [1] * n and np.array_equal(on, on_profile)
+    assert np.array_equal(ranks, ref['ranks'])
+    assert S.tobytes() == S.T.copy().tobytes()
+    S2, none_r, none_on, _ = eng.node_correlations(keys, lengths, freq)
+    assert none_r is None and none_on is None and S2.tobytes() == S.tobytes()
+    bad = corr_ref.s_errors_beyond_bound(S, ref['S'], n)
+    assert not bad, bad[:5]
+    diag = np.array([int(ref['S'][a, a]) for a in range(m)], object)
+    assert all((S[a, a] > 0) == (diag[a] > 0) and (S[a, a] == 0) == (diag[a] == 0) for a in range(m))
+    rho = corr_ref.rho_of_s(S)
+    assert np.array_equal(np.isnan(rho), np.isnan(rho_ref))
+    ok = ~np.isnan(rho_ref)
+    worst = float(np.max(np.abs(rho[ok] - rho_ref[ok]))) if ok.any() else 0.0
+    print('n = {} nodes = {} T = {}: max |rho - rho_exact| = {:.3g}'.format(n, m, ref['total'], worst))
+    assert worst <= 1e-9
+    return S, ref
+
+
+def case_identity(eng, n_nodes, count, weights, constant=True, seed=1):
+    constant_node = n_nodes // 2 if constant and n_nodes > 1 else None
+    keys = identity_keys(n_nodes, count, seed, constant_node)
+    assert len(keys) == count
+    on_want = np.array([[(k >> i) & 1 for i in range(n_nodes)] for k in keys], np.uint32)
+    expect = set()
+    if constant_node is not None and count > 1:
+        expect.add('nan')
+    if count > 2 and n_nodes > 1:
+        expect.add('ties')
+    if count >= 16 and n_nodes >= 5:
+        expect.add('rho')
+    S, ref = check_table(eng, identity_text(n_nodes), keys, [1] * count, frequencies(weights, count), expect)
+    on, _, _ = eng.attractor_profile(keys, [1] * count, states=False)
+    assert np.array_equal(on, on_want)                                    # on-counts of fixed points are the key bits
+    if count == 1:
+        assert not S.any()                                                # one attractor: an all-zero matrix
+    return S
+
+
+def case_rings(eng, weights):
+    keys, lengths = rings_table()
+    assert max(lengths) == 210 and {1, 2, 3, 4, 6, 10, 210} <= set(lengths)
+    _, ref = check_table(eng, rings_text(), keys, lengths, frequencies(weights, len(keys)), {'ties', 'lengths', 'rho'})
+    # node 0 (ring 2, filling 10): 1/2, 3/6, 5/10, ... 105/210 and the 2/4 of the cycle stated twice over: one tie group
+    half = [q for q, k in enumerate(keys) if k & 0b11 in (0b01, 0b10)]
+    assert len({lengths[q] for q in half}) >= 8 and len({ref['rank2'][q, 0] for q in half}) == 1
+
+
+def case_lfsr(eng, weights):
+    keys, lengths = lfsr_table()
+    check_table(eng, lfsr_text(), keys, lengths, frequencies(weights, len(keys)), {'ties', 'lengths', 'rho'})
+
+
+NARROW_CASES = (
+    [('id_n{}_a{}'.format(m, a), functools.partial(case_identity, n_nodes=m, count=a, weights=w))
+     for m, a, w in ((1, 2, 'ones'), (5, 1, 'ones'), (5, 2, 'mixed'), (5, 3, 'ones'), (5, 4, 'top'), (5, 5, 'mixed'),
+                     (16, 1023, 'ones'), (16, 1024, 'mixed'), (16, 1025, 'ones'), (17, 40, 'top'), (64, 100, 'mixed'),
+                     (65, 70, 'ones'), (130, 50, 'mixed'),
+                     (17, CHUNK - 1, 'ones'), (17, CHUNK, 'ones'), (17, CHUNK + 1, 'mixed'), (17, 2 * CHUNK + 3, 'ones'))] +
+    [('rings_' + w, functools.partial(case_rings, weights=w)) for w in ('ones', 'mixed', 'top')] +
+    [('lfsr_' + w, functools.partial(case_lfsr, weights=w)) for w in ('ones', 'mixed')])
+WIDE_CHILD_CASE = 'id_n64_a100'
+
+
+@pytest.fixture(scope='module')
+def eng():
+    with Engine(0) as e:
+        yield e
+
+
+@pytest.mark.parametrize('name', [name for name, _ in NARROW_CASES])
+def test_narrow(eng, name):
+    dict(NARROW_CASES)[name](eng)
+    assert not eng.wide
+
+
+def test_two_column_batches(eng, monkeypatch):
+    """17 columns of 100 attractors, 500 cells per batch: batches of 5, 5, 5 and 2 columns give the matrix of one batch"""
+    whole = case_identity(eng, 17, 100, 'mixed')
+    monkeypatch.setenv('BSX_CORR_BATCH_CELLS', '500')
+    launches_whole = eng.corr_stats['kernel_launches']
+    parts = case_identity(eng, 17, 100, 'mixed')
+    assert eng.corr_stats['kernel_launches'] == launches_whole + 3 * 4      # (observe, sort, two rank walks per extra batch)
+    assert parts.tobytes() == whole.tobytes()
+
+
+@pytest.mark.parametrize('n_nodes,count', [(257, 64), (1024, 33)])
+def test_wide_family(eng, n_nodes, count):
+    case_identity(eng, n_nodes, count, 'ones' if n_nodes == 1024 else 'mixed')
+    assert eng.wide
+
+
+def test_a_narrow_case_on_the_wide_family():
+    env = dict(os.environ, BSX_WIDE='1')
+    res = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0, res.stdout[-4000:] + res.stderr[-4000:]
+    assert res.stdout.strip().endswith('wide family: {} ok'.format(WIDE_CHILD_CASE))
+
+
+# ---- refusals and side effects --------------------------------------------------------------------------------------------
+
+def test_refusals(eng):
+    _, net, space = compiled(identity_text(5))
+    eng.set_problem(net, space)
+    keys, lengths = [1, 2, 4], [1, 1, 1]
+
+    def refused(k, l, f, status):
+        eng.corr_stats = None
+        with pytest.raises(EngineError) as err:
+            eng.node_correlations(k, l, f)
+        assert err.value.status == status
+
+    refused(keys, lengths, [1 << 61, 1 << 61, 1], ERR_RANGE_TOO_LARGE)          # T = 2^62 + 1
+    refused(keys, lengths, [(1 << 62) - 2, 1, 1], ERR_RANGE_TOO_LARGE)          # T = 2^62
+    refused(keys, lengths, [1, 1 << 64, 1], ERR_RANGE_TOO_LARGE)                # a high word
+    refused(keys, lengths, [1, 0, 1], ERR_INVALID)
+    refused([1, 1 << 5, 4], lengths, [1, 1, 1], ERR_INVALID)                    # a key bit at n_nodes
+    refused(keys, [1, 0, 1], [1, 1, 1], ERR_INVALID)
+    S, _, _, _ = eng.node_correlations(keys, lengths, [(1 << 62) - 3, 1, 1])    # T = 2^62 - 1 is served
+    assert S[0, 0] > 0
+    # the raw call: null outputs are refused, and a refused call has launched nothing
+    key_words = np.array(keys, np.uint64)
+    lens = np.array(lengths, np.uint64)
+    freq = np.array([[1, 0]] * 3, np.uint64)
+    out = np.zeros((5, 5), np.float64)
+    for f_ptr, s_ptr in ((None, _lib.ptr(out)), (_lib.ptr(freq), None)):
+        st = _lib.Stats()
+        st.kernel_launches = 99
+        rc = eng._lib.bsx_run_node_correlations(eng._h, _lib.ptr(key_words), 1, _lib.ptr(lens), f_ptr, 3, s_ptr, None, None, None,
+                                                ctypes.byref(st))
+        assert rc == ERR_INVALID and st.kernel_launches == 0
+    zero = np.array([[1, 0], [0, 0], [1, 0]], np.uint64)
+    st = _lib.Stats()
+    rc = eng._lib.bsx_run_node_correlations(eng._h, _lib.ptr(key_words), 1, _lib.ptr(lens), _lib.ptr(zero), 3, _lib.ptr(out), None,
+                                            None, None, ctypes.byref(st))
+    assert rc == ERR_INVALID and st.kernel_launches == 0 and not out.any()
+    # n = 0: BSX_OK, nothing written
+    out[:] = 5.0
+    rc = eng._lib.bsx_run_node_correlations(eng._h, None, 1, None, None, 0, _lib.ptr(out), None, None, None, ctypes.byref(st))
+    assert rc == 0 and (out == 5.0).all() and st.kernel_launches == 0
+    # before a network and a problem space are set
+    with Engine(eng.device) as bare:
+        rc = bare._lib.bsx_run_node_correlations(bare._h, _lib.ptr(key_words), 1, _lib.ptr(lens), _lib.ptr(freq), 3, _lib.ptr(out),
+                                                 None, None, None, ctypes.byref(st))
+        assert rc == ERR_STATE
+
+
+def test_not_closed_is_reported_not_refused(eng):
+    keys, lengths = lfsr_table()
+    _, net, space = compiled(lfsr_text())
+    eng.set_problem(net, space)
+    S, _, on, closed = eng.node_correlations(keys[:4], [1022, 1, 1023, 1], [1, 2, 3, 4], activity=True)
+    assert closed.tolist() == [0, 1, 1, 1]
+    on_profile, _, closed_profile = eng.attractor_profile(keys[:4], [1022, 1, 1023, 1], states=False)
+    assert np.array_equal(on, on_profile) and closed_profile.tolist() == [0, 1, 1, 1]
+
+
+def test_handle_state_is_left_alone(eng):
+    """as test_gpu_profile.py: the attract after a correlation call finds the table again and is as cheap as a repeat"""
+    from test_gpu_profile import random_text
+    _, net, space = compiled(random_text(64, 1, n_any=16))
+    eng.set_problem(net, space)
+    first = eng.attract(0, 1 << 12)
+    again = eng.attract(0, 1 << 12)
+    keys = [int(words_to_code(r['key'])) for r in first.table]
+    lengths = [int(r['length']) for r in first.table]
+    assert len(keys) >= 2
+    eng.node_correlations(keys, lengths, [int(r['count']) for r in first.table])
+    after = eng.attract(0, 1 << 12)
+    order = lambda t: np.sort(t, order=['key', 'length'])
+    assert np.array_equal(order(after.table), order(first.table)) and after.n_no_attractor == first.n_no_attractor
+    cold, warm, got = (r.stats['executed_steps'] for r in (first, again, after))
+    assert warm < cold and got <= warm + (cold - warm) // 4
+
+
+# ---- host layer -----------------------------------------------------------------------------------------------------------
+
+def compare_paths(eng, attractors, some_p_above_threshold=True):
+    dev = find_node_correlations(attractors, engine=eng, device=True)
+    host = find_node_correlations(attractors, engine=eng, device=False)
+    assert np.array_equal(np.isnan(dev[0]), np.isnan(host[0])) and np.array_equal(np.isnan(dev[1]), np.isnan(host[1]))
+    ok = ~np.isnan(host[0])
+    assert np.max(np.abs(dev[0][ok] - host[0][ok])) <= 1e-9
+    big = ok & (host[1] > 1e-12)
+    assert big.any() == some_p_above_threshold              # (two attractors: every rho is +-1 and every P is 0)
+    if big.any():
+        assert np.max(np.abs(dev[1][big] - host[1][big]) / host[1][big]) <= 1e-6
+    return dev, host
+
+
+def test_find_node_correlations_on_example2(eng):
+    path = os.path.join(GOLDEN, 'examples', 'output3_example2', 'example2.yaml')
+    cfg = parse_input_text(open(path).read(), float('inf'), Mode.ATTRACT)
+    attractors, _, _, _ = attract_master(eng, cfg['origin simulation problem'], cfg['simulation problem variations'],
+                                         cfg['incoming node lists'], cfg['truth tables'], float('inf'), float('inf'),
+                                         cfg['total combination count'], with_states=True, with_activity=True)
+    assert len(attractors) == 2
+    assert not attractor_analysis.uses_device(len(attractors), len(cfg['node names']), eng)      # the size rule: host path
+    compare_paths(eng, attractors, some_p_above_threshold=False)
+
+
+def and_network_text(n_identity):
+    """identity nodes, then one node = first AND second identity node, then a constant node"""
+    n = n_identity + 2
+    preds = [[i] for i in range(n_identity)] + [[0, 1], []]
+    masks = [0b10] * n_identity + [0b1000, 0]
+    return yaml_of(preds, masks, ['any'] * n_identity + ['0', '0'])
+
+
+def test_find_node_correlations_on_4096_attractors(eng):
+    _, net, space = compiled(and_network_text(12))
+    eng.set_problem(net, space)
+    attractors = [AggregatedAttractor(x | ((x & (x >> 1) & 1) << 12), 1, 1 + (x * 7) % 13, 0, 0) for x in range(4096)]
+    dev, host = compare_paths(eng, attractors)
+    assert np.isnan(dev[0][13]).all() and 0 < abs(dev[0][0, 12]) < 1
+    bad = [AggregatedAttractor(1 << 12, 1, 1, 0, 0)] + attractors[1:]                # 1 << 12 is no fixed point (0 AND 0 = 0)
+    with pytest.raises(RuntimeError, match=str(1 << 12)):
+        find_node_correlations(bad, engine=eng, device=True)
+
+
+def run_cli(args, out_dir):
+    cmd = [sys.executable, '-m', 'boolsi_amd'] + args + ['-o', out_dir]
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout + res.stderr
+    return res.stdout
+
+
+def test_cli_example2_stays_on_the_host_path(tmp_path):
+    src = os.path.join(GOLDEN, 'examples', 'output3_example2')
+    out = run_cli(['attract', os.path.join(src, 'example2.yaml')], str(tmp_path))
+    assert 'Computing node correlations...' in out and 'on the device' not in out
+    assert open(tmp_path / 'node_correlations.csv', 'rb').read() == open(os.path.join(src, 'node_correlations.csv'), 'rb').read()
+
+
+def test_cli_large_table_takes_the_device_path(eng, tmp_path):
+    text = and_network_text(9)                              # 512 attractors x 11 nodes = 5632 cells
+    cfg, net, space = compiled(text)
+    assert 512 * 11 >= attractor_analysis.DEVICE_CORRELATION_CELLS
+    (tmp_path / 'net.yaml').write_text(text)
+    out = run_cli(['attract', str(tmp_path / 'net.yaml'), '-x'], str(tmp_path / 'out'))
+    assert 'Found 512 attractors.' in out and 'Computing node correlations on the device (512 attractors x 11 nodes)' in out
+    rows = list(csv.reader(open(tmp_path / 'out' / 'node_correlations.csv')))
+    # the forced host path, in process
+    from boolsi_amd.output import output_node_correlations
+    attractors, _, _, _ = attract_master(eng, cfg['origin simulation problem'], cfg['simulation problem variations'],
+                                         cfg['incoming node lists'], cfg['truth tables'], float('inf'), float('inf'),
+                                         cfg['total combination count'], with_states=False, with_activity=True)
+    rho, p = find_node_correlations(attractors, engine=eng, device=False)
+    output_node_correlations(rho, p, 0.05, cfg['node names'], str(tmp_path / 'host'))
+    want = list(csv.reader(open(tmp_path / 'host' / 'node_correlations.csv')))
+    assert [r[:2] for r in rows] == [r[:2] for r in want] and len(rows) == 1 + 11 * 10 // 2
+    absent = [r for r in rows[1:] if r[2] == 'nan']
+    assert len(absent) == 10 and all(synth.node_name(10) in r[:2] for r in absent)       # the constant node's pairs
+    for got, exp in zip(rows[1:], want[1:]):
+        if exp[2] != 'nan':
+            assert abs(float(got[2]) - float(exp[2])) <= 1e-9
+
+
+if __name__ == '__main__':
+    # the child process of test_a_narrow_case_on_the_wide_family: BSX_WIDE=1 lowers every network to the wide family
+    assert os.environ.get('BSX_WIDE', '') == '1'
+    logging.basicConfig(level=logging.WARNING)
+    with Engine(0) as engine:
+        dict(NARROW_CASES)[WIDE_CHILD_CASE](engine)
+        assert engine.wide
+        print('wide family: {} ok'.format(WIDE_CHILD_CASE), flush=True)
