@@ -23,12 +23,16 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 EXPORTS = (
     'bsx_create', 'bsx_destroy', 'bsx_last_error', 'bsx_status_string', 'bsx_device_info', 'bsx_network_info',
     'bsx_set_network', 'bsx_set_problem_space', 'bsx_run_attract', 'bsx_run_attract2', 'bsx_run_attract_wide', 'bsx_run_attract_fgraph', 'bsx_run_target',
-    'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_run_attractor_profile', 'bsx_run_node_correlations', 'bsx_synchronize',
+    'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_run_attractor_profile', 'bsx_run_node_correlations', 'bsx_run_attractor_transitions',
+    'bsx_synchronize',
     'bsx_comm_unique_id', 'bsx_comm_init', 'bsx_comm_allgather', 'bsx_comm_destroy',
 )
 COMM_ID_BYTES = 128
 CORR_CHUNK = 4096           # BSX_CORR_CHUNK: attractors per covariance partial of bsx_run_node_correlations
 CORR_MAX_CELLS = 1 << 31    # BSX_CORR_MAX_CELLS
+TRANS_MAX_STATES = 1 << 28  # BSX_TRANS_MAX_STATES
+TRANS_OUTSIDE = 0xFFFFFFFE  # BSX_TRANS_OUTSIDE
+TRANS_UNRESOLVED = 0xFFFFFFFF   # BSX_TRANS_UNRESOLVED
 
 
 class EngineUnavailable(RuntimeError):
@@ -46,7 +50,10 @@ class Index(C.Structure):
 
 
 # bsx_status values the host layers react to (include/bsx.h)
+ERR_INVALID = -1
 ERR_UNSUPPORTED = -4
+ERR_TABLE_FULL = -5
+ERR_STEP_LIMIT = -6
 ERR_RANGE_TOO_LARGE = -9
 
 
@@ -98,6 +105,8 @@ ATTR_REC2W = np.dtype([('key', '<u8', (MAX_STATE_WORDS,)), ('length', '<u8'), ('
 PROBLEM_REC = np.dtype([('key', '<u8', (MAX_WORDS,)), ('length', '<u8'), ('trajectory_l', '<u8'),
                         ('found', '<u4'), ('pad', '<u4')])
 HIT = np.dtype([('offset', '<u8'), ('t', '<u8')])
+# bsx_trans_edge (bsx_run_attractor_transitions)
+TRANS_EDGE = np.dtype([('src', '<u4'), ('dst', '<u4'), ('count', '<u8'), ('sum_mu', '<u8')])
 FIXED = np.dtype([('node', '<u4'), ('value', '<u4')])
 FIXED_VAR = np.dtype([('node', '<u4'), ('range', '<u4')])
 PERT = np.dtype([('t', '<u4'), ('node', '<u4'), ('value', '<u4')])
@@ -146,6 +155,7 @@ def load():
     lib.bsx_run_trajectories.argtypes = [vp, C.POINTER(Index), vp, vp, u64, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_attractor_profile.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_node_correlations.argtypes = [vp, vp, u32, vp, vp, u64, vp, vp, vp, vp, C.POINTER(Stats)]
+    lib.bsx_run_attractor_transitions.argtypes = [vp, vp, u32, vp, u64, u64, vp, u64, C.POINTER(u64), vp, vp, C.POINTER(Stats)]
     lib.bsx_synchronize.argtypes = [vp]
     lib.bsx_comm_unique_id.argtypes = [vp, vp, u32]
     lib.bsx_comm_init.argtypes = [vp, vp, u32, C.c_int, C.c_int]

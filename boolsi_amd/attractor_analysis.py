@@ -8,6 +8,7 @@ DESIGN.md "Node correlations") that returns S = sum_q f_q d2_qa d2_qb over exact
 their matrix to correlation_statistics(), which forms rho, t and the p-values.
 """
 import logging
+from math import inf
 
 import numpy as np
 from scipy import stats
@@ -100,3 +101,23 @@ def find_node_correlations(attractors, engine=None, device=None):
     frequencies = np.array([a.frequency for a in attractors])
     log.info('Computing node correlations...')
     return compute_frequency_spearmanrho(observations, frequencies)
+
+
+def attractor_transitions(engine, attractors, max_t=inf):
+    """
+    Stability of the attractors of a finished table under a single flip of one node (Engine.attractor_transitions): for
+    every attractor, every one of its states and every node that the origin problem does not fix, the node is flipped
+    once and the network followed until it is on a cycle again.
+    -> (edges, n_free): the engine's edge records (src and dst index `attractors`; dst may be _lib.TRANS_OUTSIDE or
+    _lib.TRANS_UNRESOLVED) and the number of free nodes, so that attractor q has length_q * n_free flips.
+    None on the wide-state family, which the device call does not support.
+    """
+    if engine.wide:
+        return None
+    edges, _, closed = engine.attractor_transitions([a.key for a in attractors], [a.length for a in attractors], max_t=max_t,
+                                                    edge_cap=max(1, min(1 << 24, len(attractors) * (len(attractors) + 2))))
+    for a, ok in zip(attractors, closed):
+        if not ok:
+            raise RuntimeError('attractor {} does not return to its key state after {} steps'.format(a.key, a.length))
+    n_free = engine.net.n_nodes - len({int(node) for node in engine.space.fixed[:, 0]})
+    return edges, n_free

@@ -170,6 +170,9 @@ def simulate(**kw):
               help='Turn off outputting attractors.')
 @click.option('-p', '--p-value', 'p_value', type=click.FLOAT, default=0.05,
               help='p-value threshold for statistical significance of node correlations. Defaults to 0.05.')
+@click.option('--transitions', 'transitions', is_flag=True,
+              help='Also flip every free node once in every state of every attractor found and write where the '
+                   'network goes to attractor_transitions.csv.')
 def attract(**kw):
     def body(run):
         from .attract import attract_master, profile_attractors
@@ -206,6 +209,14 @@ def attract(**kw):
             _, fixed_nodes, _ = cfg['origin simulation problem']
             output_attractors(attractors, total_frequency, fixed_nodes, cfg['node names'],
                               cfg['total combination count'], max_len, max_t, run.out)
+        if kw['transitions']:
+            from .attractor_analysis import attractor_transitions
+            from .output import output_attractor_transitions
+            found = attractor_transitions(engine, attractors, max_t)
+            if found is None:
+                logging.getLogger().info('Attractor transitions are not available for networks of more than 256 nodes.')
+            else:
+                output_attractor_transitions(found[0], [a.length for a in attractors], found[1], run.out)
     _guarded(kw, body)
 
 

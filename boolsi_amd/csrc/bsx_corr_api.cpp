@@ -48,7 +48,7 @@ extern "C" int bsx_run_node_correlations(bsx_handle h, const uint64_t* keys, uin
     bsx_stats pst{};
     const int rc = h->wide ? wide_run_profile(h, keys, key_stride, lengths, n, on_counts, nullptr, nullptr, 0, closed, sum_len, &pst, &d_on)
                            : profile_lanes(h, keys, key_stride, lengths, n, on_counts, nullptr, nullptr, 0, closed, sum_len, &pst,
-                                           t_begin, &d_on);
+                                           t_begin, &d_on, nullptr);
     if (rc) return rc;
 
     // columns per batch: the sort's and the ranks' working set is 32 bytes per cell of a batch plus rocprim's own

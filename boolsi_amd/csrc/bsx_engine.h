@@ -42,6 +42,13 @@ struct DevBuf {
     }
 };
 
+// what profile_lanes leaves on the device for a caller that goes on enqueueing behind it (keep_states)
+struct ProfileKeep {
+    DevBuf<uint64_t> keys, lengths, offsets, states;
+    DevBuf<uint8_t> closed;
+    uint32_t launches = 0;
+};
+
 }  // namespace bsx
 
 struct bsx_engine {
@@ -174,13 +181,14 @@ int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, co
                      uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
                      uint64_t sum_len, bsx_stats* stats, DevBuf<uint32_t>* keep_on);
 // bsx_profile_api.cpp: the checks and the per-lane family of bsx_run_attractor_profile, shared with
-// bsx_run_node_correlations (bsx_corr_api.cpp), which keeps the on-counts on the device (keep_on)
+// bsx_run_node_correlations (bsx_corr_api.cpp), which keeps the on-counts on the device (keep_on), and with
+// bsx_run_attractor_transitions (bsx_trans_api.cpp), which keeps the states there (keep_states)
 int profile_check_args(bsx_handle h, const char* who, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths,
                        uint64_t n, const uint64_t* states, const uint64_t* state_offsets, uint64_t* sum_len_out,
                        uint64_t* state_words_out);
 int profile_lanes(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
                   uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
-                  uint64_t sum_len, bsx_stats* stats, double t_begin, DevBuf<uint32_t>* keep_on);
+                  uint64_t sum_len, bsx_stats* stats, double t_begin, DevBuf<uint32_t>* keep_on, ProfileKeep* keep_states);
 }  // namespace bsx
 
 static inline int fail(bsx_handle h, int status, const std::string& msg) {

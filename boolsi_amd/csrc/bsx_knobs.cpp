@@ -45,6 +45,8 @@ Knobs Knobs::from_env() {
     k.wide_step_limit = kWideStepLimit;
     if (const char* e = std::getenv("BSX_WIDE_STEP_LIMIT")) k.wide_step_limit = std::max(16u, std::min(kWideStepLimit, (uint32_t)std::atoi(e)));
     if (const char* e = std::getenv("BSX_CORR_BATCH_CELLS")) k.corr_batch_cells = std::strtoull(e, nullptr, 10);
+    k.trans_step_limit = kStepLimit;
+    if (const char* e = std::getenv("BSX_TRANS_STEP_LIMIT")) k.trans_step_limit = std::max(1u, std::min(kStepLimit, (uint32_t)std::atoi(e)));
     return k;
 }
 

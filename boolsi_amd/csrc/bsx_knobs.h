@@ -37,6 +37,7 @@ struct Knobs {
     uint64_t wide_chunk = 0;        // ... clamped where it is used (the lower bound depends on the network)
     uint32_t wide_step_limit = 0;   // BSX_WIDE_STEP_LIMIT: 16 .. kWideStepLimit (default: kWideStepLimit)
     uint64_t corr_batch_cells = 0;  // BSX_CORR_BATCH_CELLS: cells (columns x attractors) per sort batch of the node correlations (0 = not set)
+    uint32_t trans_step_limit = 0;  // BSX_TRANS_STEP_LIMIT: 1 .. kStepLimit, per walk of the attractor transitions (default: kStepLimit)
 
     static Knobs from_env();
 };

@@ -24,20 +24,27 @@ static_assert(kProfileChunk == BSX_PROFILE_CHUNK, "the header states the chunk s
 namespace bsx {
 
 // keep_on: the on-counts are counted whether or not the caller wants them on the host, and stay in *keep_on
+// keep_states: states and closure are written whether or not the caller wants them on the host, and every device
+// buffer of the call stays in *keep_states; the launches are enqueued on the handle's stream and NOT waited for, nothing
+// is copied back and `stats` is not written (bsx_trans_api.cpp goes on enqueueing behind them)
 int profile_lanes(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
                   uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words,
-                  uint8_t* closed, uint64_t sum_len, bsx_stats* stats, double t_begin, DevBuf<uint32_t>* keep_on) {
+                  uint8_t* closed, uint64_t sum_len, bsx_stats* stats, double t_begin, DevBuf<uint32_t>* keep_on,
+                  ProfileKeep* keep_states) {
     const uint32_t W = h->w64, n_nodes = h->n_nodes;
-    DevBuf<uint64_t> d_keys, d_len, d_off, d_states;
+    ProfileKeep here;
+    ProfileKeep& kept = keep_states ? *keep_states : here;
+    DevBuf<uint64_t>&d_keys = kept.keys, &d_len = kept.lengths, &d_off = kept.offsets, &d_states = kept.states;
     DevBuf<uint32_t> d_on_here;
     DevBuf<uint32_t>& d_on = keep_on ? *keep_on : d_on_here;
     const bool count_on = on_counts || keep_on;
-    DevBuf<uint8_t> d_closed;
+    DevBuf<uint8_t>& d_closed = kept.closed;
+    const bool want_states = states || keep_states, want_closed = closed || keep_states;
     HIPCHK(h, d_keys.alloc(n * key_stride));
     HIPCHK(h, hipMemcpy(d_keys.p, keys, n * key_stride * 8, hipMemcpyHostToDevice));
     HIPCHK(h, d_len.alloc(n));
     HIPCHK(h, hipMemcpy(d_len.p, lengths, n * 8, hipMemcpyHostToDevice));
-    if (states) {
+    if (want_states) {
         HIPCHK(h, d_off.alloc(n));
         HIPCHK(h, hipMemcpy(d_off.p, state_offsets, n * 8, hipMemcpyHostToDevice));
         HIPCHK(h, d_states.alloc(state_words));
@@ -46,14 +53,14 @@ int profile_lanes(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const
         HIPCHK(h, d_on.alloc(n * n_nodes));
         HIPCHK(h, hipMemsetAsync(d_on.p, 0, n * n_nodes * sizeof(uint32_t), h->stream));
     }
-    if (closed) HIPCHK(h, d_closed.alloc(n));
+    if (want_closed) HIPCHK(h, d_closed.alloc(n));
 
     ProfileParams P{};
     P.net = h->net;
     for (int w = 0; w < kMaxW32; ++w) { P.fixmask[w] = h->sp.fixmask[w]; P.fixval[w] = h->sp.fixval[w]; }
     P.w64 = W;
     P.key_stride = key_stride;
-    P.states = states ? d_states.p : nullptr;       // (offsets are relative to the whole buffer in every chunk)
+    P.states = want_states ? d_states.p : nullptr;      // (offsets are relative to the whole buffer in every chunk)
     P.ctr = h->d_ctr;
     const uint32_t cus = (uint32_t)h->prop.multiProcessorCount;
     uint32_t launches = 0;
@@ -64,12 +71,16 @@ int profile_lanes(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const
         P.count = m;
         P.keys = d_keys.p + at * key_stride;
         P.lengths = d_len.p + at;
-        P.state_offsets = states ? d_off.p + at : nullptr;
+        P.state_offsets = want_states ? d_off.p + at : nullptr;
         P.on_counts = count_on ? d_on.p + at * n_nodes : nullptr;
-        P.closed = closed ? d_closed.p + at : nullptr;
+        P.closed = want_closed ? d_closed.p + at : nullptr;
         const uint64_t block = (uint64_t)profile_block((int)h->net.nw);
         const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * 4, (m + block - 1) / block));
         HIPCHK(h, launch_profile((int)h->net.nw, (int)h->net.k_mux, h->lut_mode, dim3((uint32_t)blocks), h->shmem, h->stream, P));
+    }
+    if (keep_states) {
+        keep_states->launches = launches;
+        return BSX_OK;
     }
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     Counters ctr{};
@@ -158,5 +169,5 @@ extern "C" int bsx_run_attractor_profile(bsx_handle h, const uint64_t* keys, uin
         return wide_run_profile(h, keys, key_stride, lengths, n, on_counts, states, state_offsets, state_words, closed, sum_len,
                                 stats, nullptr);
     return profile_lanes(h, keys, key_stride, lengths, n, on_counts, states, state_offsets, state_words, closed, sum_len, stats,
-                         t_begin, nullptr);
+                         t_begin, nullptr, nullptr);
 }

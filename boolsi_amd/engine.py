@@ -242,6 +242,43 @@ class Engine:
         self._check(self._lib.bsx_run_node_correlations(self._h, keys, key_stride, lengths, frequencies, n, s_matrix, ranks,
                                                         on_counts, closed, C.byref(stats)))
 
+    def attractor_transitions(self, keys, lengths, max_t=float('inf'), edge_cap=1 << 20, node_exits=False):
+        """
+        Where every single-node flip of every cycle state of the listed attractors ends, in one device call
+        (bsx_run_attractor_transitions): attractor q = (key state code, length), walked under the origin problem's fixed
+        nodes without perturbations; one flip per (attractor, cycle state, node that the origin does not fix).
+        -> (edges, node_exits, closed):
+           edges       TRANS_EDGE records (src, dst, count, sum_mu) sorted by (src, dst); dst is a row of the table,
+                       _lib.TRANS_OUTSIDE (a cycle in no row) or _lib.TRANS_UNRESOLVED (mu + lambda > max_t); sum_mu is the
+                       sum of the recovery times of the `count` flips (0 for the two pseudo-destinations)
+           node_exits  (n, n_nodes) uint32, how many flips of node i from attractor q did not return to q; None unless asked
+           closed      uint8 array, 1 iff f^length(key) == key
+        An EngineError with status ERR_INVALID names a row that is not closed or shares a state with another row,
+        ERR_TABLE_FULL means more distinct edges than `edge_cap`, ERR_UNSUPPORTED a network on the wide-state family.
+        `trans_stats` holds the call's statistics afterwards.
+        """
+        W = self.net.n_words
+        n = len(keys)
+        ints = [int(k) for k in keys]
+        if any(k < 0 or k >> (64 * W) for k in ints):
+            raise ValueError('a key does not fit the {} words of a state'.format(W))
+        key_words = np.zeros((n, W), np.uint64)
+        for w in range(W):
+            key_words[:, w] = [(k >> (64 * w)) & _M64 for k in ints]
+        lens = np.ascontiguousarray(lengths, np.uint64)
+        if lens.shape != (n,):
+            raise ValueError('one length per key')
+        cap = _lib.T_INF if max_t is None or max_t == float('inf') else int(max_t)
+        edges = np.zeros(int(edge_cap), _lib.TRANS_EDGE)
+        exits = np.zeros((n, self.net.n_nodes), np.uint32) if node_exits else None
+        closed = np.zeros(n, np.uint8)
+        n_edges = C.c_uint64(0)
+        st = Stats()
+        self._check(self._lib.bsx_run_attractor_transitions(self._h, ptr(key_words), W, ptr(lens), n, cap, edges.ctypes.data_as(C.c_void_p),
+                                                            int(edge_cap), C.byref(n_edges), ptr(exits), ptr(closed), C.byref(st)))
+        self.trans_stats = st.as_dict()
+        return edges[:n_edges.value].copy(), exits, closed
+
     def index(self, i):
         """python int problem index -> bsx_index (split at the initial-state digits)."""
         n_any = len(self.space.any_nodes)

@@ -136,3 +136,22 @@ def output_node_correlations(Rho, P, p_value, node_names, output_dirpath):
             pairs = sorted(zip(np.argwhere(upper).tolist(), Rho[upper], P[upper]), key=key)
             for (a, b), rho, p in pairs:
                 writer.writerow([node_names[a], node_names[b], rho, p])
+
+
+def output_attractor_transitions(edges, attractor_lengths, n_free, output_dirpath):
+    """attractor_transitions.csv: where single-node flips of the attractors' states lead (Engine.attractor_transitions).
+    One row per (attractor, destination), ids as in attractor_summaries.csv; `share` is the fraction of the attractor's
+    length * n_free flips, `recovery_time_mean` the mean number of steps back onto a cycle (empty for 'outside', a cycle
+    that is not in the table, and 'unresolved', not on a cycle within the maximum simulation time)."""
+    from ._lib import TRANS_OUTSIDE, TRANS_UNRESOLVED
+    os.makedirs(output_dirpath, exist_ok=True)
+    logging.getLogger().info('Printing attractor transitions to {}...'.format(list_texts(['"attractor_transitions.csv"'])))
+    names = {TRANS_OUTSIDE: 'outside', TRANS_UNRESOLVED: 'unresolved'}
+    with open(os.path.join(output_dirpath, 'attractor_transitions.csv'), 'w', newline='', encoding='utf-8') as f:
+        writer = csv.writer(f)
+        writer.writerow([aggregated_attractor_name + '_id', 'destination_id', 'n_perturbations', 'share', 'recovery_time_mean'])
+        for e in edges:
+            src, dst, count, sum_mu = int(e['src']), int(e['dst']), int(e['count']), int(e['sum_mu'])
+            writer.writerow(['{}{}'.format(aggregated_attractor_name, src + 1),
+                             names.get(dst) or '{}{}'.format(aggregated_attractor_name, dst + 1), count,
+                             count / (int(attractor_lengths[src]) * n_free), '' if dst in names else sum_mu / count])

@@ -315,6 +315,50 @@ int  bsx_run_node_correlations(bsx_handle h, const uint64_t* keys, uint32_t key_
                                const bsx_u128* frequencies, uint64_t n, double* s_matrix, double* ranks,
                                uint32_t* on_counts, uint8_t* closed, bsx_stats* stats);
 
+/* Single-node flip transitions of a whole attractor table: is an attractor stable when one node is flipped once, and
+ * if not, where does the network go and after how many steps?  keys / key_stride / lengths / n and closed are those of
+ * bsx_run_attractor_profile.  F is the current network under the origin problem's fixed nodes, without perturbation
+ * schedule or variations (what the profile walks); s[q][j] = F^j(key_q), j < length_q; the free nodes are those the
+ * origin does not fix, n_free of them.
+ * One flip per (q, j, i), i free: x_0 = s[q][j] XOR (1 << i), x_(t+1) = F(x_t); mu = the least t with x_t on a cycle C,
+ * lambda' = |C|.  The flip is resolved iff mu + lambda' <= max_t (what bsx_run_attract reports as found for a problem
+ * whose initial state is x_0 and whose last perturbation time is 0); BSX_T_INF resolves every flip.
+ *   resolved, C is row d of the table:  edge (q, d), recovery time mu  (d == q: the flip returns)
+ *   resolved, C is in no row:           edge (q, BSX_TRANS_OUTSIDE)
+ *   not resolved:                       edge (q, BSX_TRANS_UNRESOLVED)
+ * edges: one record per distinct (src, dst) with the number of flips and the sum of their mu (0 for the two
+ *   pseudo-destinations), sorted by (src, dst); *n_edges = their number.  For every q the counts out of q add up to
+ *   length_q * n_free.  More distinct edges than edge_cap: BSX_ERR_TABLE_FULL.
+ * node_exits[q * n_nodes + i] = how many of the length_q flips of node i did not end as edge (q, q); fixed nodes 0.  (nullable)
+ * closed[q] as in bsx_run_attractor_profile.                                                                          (nullable)
+ * Refused before any flip is walked, with nothing written but the error text: everything bsx_run_attractor_profile
+ * checks; edges and n_edges non-null, n <= 2^32 - 3 (BSX_ERR_INVALID); the sum of the lengths <= BSX_TRANS_MAX_STATES
+ * (BSX_ERR_UNSUPPORTED); a row that is not closed, and two rows that share a state -- a duplicate row, or a length that
+ * is a multiple of the true period -- (BSX_ERR_INVALID, the text names the row); a network on the wide-state family
+ * (more than BSX_MAX_NODES nodes, or BSX_WIDE=1: BSX_ERR_UNSUPPORTED, the text says so).  n == 0 is BSX_OK with nothing
+ * written.  A walk that reaches the internal step limit (2^30, or BSX_TRANS_STEP_LIMIT) undecided: BSX_ERR_STEP_LIMIT;
+ * possible only when max_t is BSX_T_INF or beyond a third of that limit.
+ * The handle's problem space, cycle journal and mirror image are left alone.  stats: problems = the number of flips,
+ * state_steps = the sum of all sum_mu, executed_steps = the network updates the kernels ran (profile and walks),
+ * kernel_launches / kernel_ms over all stages; the call waits for the device once.
+ * Every output is exact and independent of the order in which the lanes arrive (integer atomics only).
+ * Device memory, from the allocation sizes: per cycle state 8 W bytes of state (W = 64-bit words per state, at most 4), a
+ * 4-byte row number and 8 to 16 bytes of table slots (4 bytes each, a power of two >= twice the states); 24 bytes per
+ * edge-table slot (a power of two >= 2 * min(edge_cap, flips, n (n + 2)) + 2) and 24 per edge record; 9 + 8 W bytes per
+ * row, 4 * n * n_nodes with node_exits.  At BSX_TRANS_MAX_STATES states of 256 nodes that is 8 + 1 + 2 = 11 GiB, and
+ * 2^36 flips in launches of 2^28. */
+#define BSX_TRANS_MAX_STATES (1ull << 28)
+#define BSX_TRANS_OUTSIDE    0xFFFFFFFEu
+#define BSX_TRANS_UNRESOLVED 0xFFFFFFFFu
+typedef struct bsx_trans_edge {
+    uint32_t src, dst;      /* rows of the table; dst may be BSX_TRANS_OUTSIDE / BSX_TRANS_UNRESOLVED */
+    uint64_t count;         /* flips */
+    uint64_t sum_mu;        /* sum of their recovery times */
+} bsx_trans_edge;
+int  bsx_run_attractor_transitions(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
+                                   uint64_t max_t, bsx_trans_edge* edges, uint64_t edge_cap, uint64_t* n_edges,
+                                   uint32_t* node_exits, uint8_t* closed, bsx_stats* stats);
+
 /* Blocks until all work of the handle's stream is done (bench.py's timing fence). */
 int  bsx_synchronize(bsx_handle h);
 

@@ -4,6 +4,8 @@ Register / spill / scratch report of every gfx950 kernel of the engine, from the
 (hipcc -Rpass-analysis=kernel-resource-usage): one CSV row per kernel instantiation.
 
     python tools/kernel_resources.py > profiles/r03_kernel_resources.csv        (no GPU needed; ~4 minutes, 8 jobs)
+    python tools/kernel_resources.py bsx_trans > profiles/attractor_transitions_kernel_resources.csv
+                                                            (only the files whose name starts with the argument)
 
 Columns: file, kernel (demangled), vgprs, agprs, sgprs, sgpr_spills, vgpr_spills, scratch_bytes_per_lane,
 occupancy_waves_per_simd, static_lds_bytes (the dynamic LDS is chosen at launch, bsx_api.cpp).
@@ -42,6 +44,10 @@ LAUNCHED = {
     'bsx::k_wide_reduce_attract': 'wide networks: attract records of a chunk into the HBM table (behind every k_wide attract launch)',
     'bsx::k_wide_reduce_drain': 'wide networks: table to dense records, once per attract call',
     'bsx::k_wide_reduce_target': 'wide networks: hits and first-hit histogram of a chunk (target summary)',
+    'bsx::k_trans_build': 'attractor transitions: cycle-state table in HBM, once per call',
+    'bsx::k_trans_drain': 'attractor transitions: edge table to records, once per call',
+    'bsx::k_trans_walk<1, 2, 1>': 'attractor transitions: tools/bench_transitions.py, table "mixed" (n = 16)',
+    'bsx::k_trans_walk<2, 2, 1>': 'attractor transitions: tools/bench_transitions.py, table "north_star" (n = 64, K = 2)',
 }
 
 
@@ -70,7 +76,7 @@ def one(path):
 
 
 def main():
-    files = sorted(glob.glob(os.path.join(CSRC, '*.hip')))
+    files = sorted(glob.glob(os.path.join(CSRC, (sys.argv[1] if len(sys.argv) > 1 else '') + '*.hip')))
     with concurrent.futures.ThreadPoolExecutor(max_workers=int(os.environ.get('JOBS', '8'))) as ex:
         rows = [r for part in ex.map(one, files) for r in part]
     names = subprocess.run([CXXFILT], input='\n'.join(r['mangled'] for r in rows), capture_output=True, text=True).stdout.splitlines()
