@@ -372,6 +372,10 @@ int evaluate_chain(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, 
             std::fprintf(stderr, "[bsx] cube 2^%u (%u digits free) at digit value %llu%s: depth %u%s, %u digits here (%u relevant), %llu classes, %llu near a cycle, %llu unresolved\n",
                          ch.c1.a, ch.c1.n_free, (unsigned long long)ch.c1.d_lo, ch.c1.fix_mask ? " [sub-block]" : "", l.depth, i == 0 ? " (top)" : l.per_parent ? " (per parent)" : "", l.k_bits, l.r_here,
                          (unsigned long long)classes, (unsigned long long)c.near_classes, (unsigned long long)c.straggler_classes);
+        if (h->knobs.debug && l.per_parent) {
+            const LeafProgram& prog = h->h_leaf[ch.index];
+            std::fprintf(stderr, "[bsx] per-parent level: kb %u, %u enumerated rules, %u free rules, m %u\n", prog.kb, prog.n_enum, prog.n_free, prog.m);
+        }
         if (c.straggler_overflow) { verdict = kChainGiveUp; return BSX_OK; }      // too many unresolved classes: not a space for cubes
         if (c.near_overflow) { verdict = kChainLower; lower_to = l.depth - 1; return BSX_OK; }     // start over, shallower
         // (how many classes a level lists feeds the estimate that chooses later chains' tops: near_seen below)

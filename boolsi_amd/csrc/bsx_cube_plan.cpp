@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <utility>
 
 namespace bsx {
 
@@ -144,26 +145,53 @@ void cube_levels(const HostModel& m, const DevSpace& sp, const Cube& c, uint32_t
 bool build_leaf_program(const HostModel& m, const DevSpace& sp, const std::vector<uint32_t>& added_digits, LeafProgram& L) {
     const uint32_t n = m.n_nodes;
     if (added_digits.empty() || added_digits.size() > kLeafMaxBits) return false;
+    static_assert(kLeafMaxBits <= 16 && kLeafMaxDeps <= 64, "digit_node[], the free rules' 64-bit masks (bsx_leaf.h)");
     std::memset(&L, 0, sizeof(L));
     L.kb = (uint32_t)added_digits.size();
-    std::vector<int> digit_of(n, -1);
+    std::vector<int> digit_of(n, -1);                                   // node -> position in added_digits
     for (uint32_t q = 0; q < L.kb; ++q) {
         const uint32_t node = m.any[added_digits[q]];
         digit_of[node] = (int)q;
         L.added[node >> 5] |= 1u << (node & 31);
     }
+    // the dependent rules, and which digits are entangled: read by a rule that reads another added digit as well (from the
+    // wiring alone, as `dependent` is)
+    std::vector<uint32_t> dep_nodes, dep_digits;                        // per dependent rule: node, the added digits it reads (mask)
+    uint32_t entangled = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        bool dependent = false;
+        uint32_t reads = 0;
         const uint32_t k = m.pred_offsets[i + 1] - m.pred_offsets[i];
         const uint32_t* preds = m.pred_idx.data() + m.pred_offsets[i];
         if (!((sp.fixmask[i >> 5] >> (i & 31)) & 1u))                 // (a fixed node's rule is a constant, model.py:45-47)
-            for (uint32_t j = 0; j < k; ++j) dependent = dependent || digit_of[preds[j]] >= 0;
-        if (!dependent) { L.indep[i >> 5] |= 1u << (i & 31); continue; }
-        if (k > kLeafMaxK || L.n_dep == kLeafMaxDeps) return false;
+            for (uint32_t j = 0; j < k; ++j) if (digit_of[preds[j]] >= 0) reads |= 1u << digit_of[preds[j]];
+        if (!reads) { L.indep[i >> 5] |= 1u << (i & 31); continue; }
+        if (k > kLeafMaxK || dep_nodes.size() == kLeafMaxDeps) return false;
+        dep_nodes.push_back(i);
+        dep_digits.push_back(reads);
+        if (reads & (reads - 1u)) entangled |= reads;
+    }
+    // the program's numbering: entangled digits first, each class in the order of added_digits
+    std::vector<uint32_t> number(L.kb, 0);
+    L.m = (uint32_t)__builtin_popcount(entangled);
+    for (uint32_t q = 0, e = 0, f = L.m; q < L.kb; ++q) {
+        number[q] = ((entangled >> q) & 1u) ? e++ : f++;
+        L.digit_node[number[q]] = (uint16_t)m.any[added_digits[q]];
+    }
+    // enumerated rules in node order, then the free rules by digit (node order within a digit)
+    std::vector<std::pair<uint32_t, uint32_t>> order;                   // (0 or 1 + the free digit's number, rule)
+    for (uint32_t r = 0; r < dep_nodes.size(); ++r)
+        order.emplace_back((dep_digits[r] & entangled) ? 0u : 1u + number[(uint32_t)__builtin_ctz(dep_digits[r])], r);
+    std::sort(order.begin(), order.end());
+    for (const auto& o : order) {
+        const uint32_t i = dep_nodes[o.second];
+        const uint32_t k = m.pred_offsets[i + 1] - m.pred_offsets[i];
+        const uint32_t* preds = m.pred_idx.data() + m.pred_offsets[i];
         LeafDep& d = L.dep[L.n_dep++];
         d.node = (uint16_t)i;
-        d.k = (uint16_t)k;
-        for (uint32_t j = 0; j < k; ++j) d.in[j] = digit_of[preds[j]] >= 0 ? (uint16_t)(0x8000u | (uint32_t)digit_of[preds[j]]) : (uint16_t)preds[j];
+        d.k = (uint16_t)(o.first ? k | ((o.first - 1u) << 8) : k);
+        (o.first ? L.n_free : L.n_enum)++;
+        for (uint32_t j = 0; j < k; ++j)
+            d.in[j] = digit_of[preds[j]] >= 0 ? (uint16_t)(0x8000u | number[(uint32_t)digit_of[preds[j]]]) : (uint16_t)preds[j];
         d.tt = (uint32_t)(m.tt0[i] & ((1ull << (1u << k)) - 1ull));   // inputs beyond k: their selectors are 0 (the low half)
     }
     return true;

@@ -182,14 +182,22 @@ static_assert(sizeof(LevelDesc) * (kMaxChainBlocks + kMaxChains + 1) <= kPublish
 constexpr uint32_t kLeafMaxDeps = 64;       // dependent nodes the program holds (more: the per-child pass)
 constexpr uint32_t kLeafMaxBits = 14;       // digits the level may add (the children are evaluated 512 at a time)
 constexpr uint32_t kLeafMaxK = 4;           // inputs of a dependent node's rule
+// Not all 2^kb children are enumerated (bsx_leaf.h): a digit that some dependent rule reads together with another added
+// digit is ENTANGLED, the others are FREE.  The program numbers the digits itself -- the m entangled ones 0 .. m - 1 in the
+// order of the level's digit list, then the free ones -- and holds two rule lists: the ENUMERATED rules (they read an
+// entangled digit), evaluated bit-sliced over the 2^m assignments of the entangled digits, and the FREE rules (one added
+// digit, a free one), grouped by digit, each of which allows that digit's value 0, 1, both or neither: a factor.
 struct LeafDep {
-    uint16_t in[kLeafMaxK];     // input j: 0x8000 | q = the level's added digit q (child-index bit q), else the node whose PARENT bit it is
+    uint16_t in[kLeafMaxK];     // input j: 0x8000 | q = the level's added digit q (program numbering), else the node whose PARENT bit it is
     uint16_t node;              // the node this rule computes
-    uint16_t k;                 // inputs, 1 .. kLeafMaxK
+    uint16_t k;                 // low byte: inputs, 1 .. kLeafMaxK; high byte, free rules: the digit q the rule reads
     uint32_t tt;                // truth table, bit idx = output when input j is (idx >> j) & 1
 };
 struct LeafProgram {
-    uint32_t kb, n_dep;
+    uint32_t kb, n_dep;         // digits the level adds; rules = n_enum + n_free
+    uint32_t m, n_enum, n_free; // entangled digits; dep[0 .. n_enum) enumerated, dep[n_enum .. n_dep) free, by ascending digit
+    uint32_t pad;
+    uint16_t digit_node[16];    // the node of digit q in the program's numbering (host side: debugging, tests; kLeafMaxBits <= 16)
     uint32_t indep[kMaxW32];    // node bits whose first update does not depend on an added digit
     uint32_t added[kMaxW32];    // node bits of the added digits
     LeafDep dep[kLeafMaxDeps];

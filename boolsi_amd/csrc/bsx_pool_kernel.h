@@ -3,6 +3,7 @@
 // dispatch over the width in bsx_pool.hip)
 #pragma once
 #include "bsx_kernels_common.h"
+#include "bsx_leaf.h"
 
 namespace bsx {
 
@@ -71,17 +72,6 @@ __device__ __forceinline__ void deposit_runs(const DevSpace& sp, uint64_t d, uin
     }
 }
 
-// Per-parent level (bsx_device.h: LeafProgram): a batch of 64 parents with all their children is a long piece of serial work
-// for one wave (0.15 ms at 512 children each) while most waves of a launch have nothing to do, so the children -- in units
-// of one 32-children word -- are shared out over a power of two of work items per batch, enough for two per wave.
-__device__ __forceinline__ uint32_t leaf_parts(uint32_t kb, unsigned long long listed, uint64_t n_waves) {
-    const uint32_t units = kb > 5u ? 1u << (kb - 5u) : 1u;
-    const uint64_t batches = (listed + 63ull) / 64ull;
-    uint32_t parts = 1;
-    while (parts < units && batches * parts < 2ull * n_waves) parts <<= 1;
-    return parts;
-}
-
 // CUBE = true: the cube-pass build of the kernel (P.merge == 3): member counts only, no member masks, no
 // per-problem records; kept apart so that neither build carries the other's registers.
 // LOWER = true (with CUBE): the build for the lower levels of a chained cascade -- entry-based passes, whose classes are all
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
             n_items = P.level_in->abort ? 0ull : listed << P.entry_shift;
             if constexpr (LOWER) {
                 // per-parent level: the children of a batch of 64 parents are shared out over `parts` work items (below)
-                if (P.leaf && n_items) n_items = ((listed + 63ull) & ~63ull) * leaf_parts(P.leaf->kb, listed, (uint64_t)gridDim.x * kPoolWaves);
+                if (P.leaf && n_items) n_items = ((listed + 63ull) & ~63ull) * leaf_parts(P.leaf->m, listed, (uint64_t)gridDim.x * kPoolWaves);
             }
             if (n_items == 0) return;                       // nothing was handed down (or the level above overflowed)
             const uint64_t n_waves = (uint64_t)gridDim.x * kPoolWaves;
@@ -420,11 +410,8 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
         if (P.leaf) {
             // ---- depth-1 level evaluated per parent (bsx_device.h: LeafProgram).  Work items are the listed entries themselves.
             const LeafProgram* const L = P.leaf;
-            const uint32_t kb = L->kb, n_dep = L->n_dep;
-            // (the children are taken 512 at a time: 16 words of 32; digits 9.. of the child index number the pieces)
-            const uint32_t kb_in = kb < 9u ? kb : 9u;
-            const uint32_t n_words = kb_in > 5u ? 1u << (kb_in - 5u) : 1u;                     // <= 16
-            const uint32_t word_mask = kb_in >= 5u ? 0xFFFFFFFFu : (1u << (1u << kb_in)) - 1u;  // children in a word
+            // (the count itself is bsx_leaf.h: m entangled digits enumerated, the free digits a factor)
+            const uint32_t kb = L->kb, n_dep = L->n_dep, m = L->m, n_enum = L->n_enum, n_free = L->n_free;
             uint32_t indep[NW], added[NW];
 #pragma unroll
             for (int w = 0; w < NW; ++w) { indep[w] = L->indep[w]; added[w] = L->added[w]; }
@@ -461,9 +448,8 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
             const uint32_t n_occupied = __builtin_amdgcn_readfirstlane(lc[1]);
             // work item = (parent, part of its children): items [part * listed64, (part + 1) * listed64) are part `part` of all parents
             const unsigned long long listed = P.level_in->n_entries, listed64 = (listed + 63ull) & ~63ull;
-            const uint32_t parts = leaf_parts(kb, listed, (uint64_t)gridDim.x * kPoolWaves);
-            const uint32_t units_per_part = (kb > 5u ? 1u << (kb - 5u) : 1u) / parts;         // 32-children words
-            const uint32_t children_per_part = kb > 5u ? units_per_part * 32u : 1u << kb;
+            const uint32_t parts = leaf_parts(m, listed, (uint64_t)gridDim.x * kPoolWaves);
+            const uint32_t children_per_part = leaf_children_per_part(kb, m, parts);
             for (;;) {
                 if (q.next == q.end) {
                     if (!q.more) break;
@@ -477,11 +463,6 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
                 const uint32_t part = (uint32_t)(q.next / listed64);                // uniform (shares are multiples of 64)
                 const unsigned long long pbase = q.next - (unsigned long long)part * listed64;
                 const bool lv = lane < n && pbase + lane < listed;
-                // this part's children: pieces [piece0, piece0 + n_pieces_here), of each the words [w0, w0 + n_words_here)
-                const uint32_t unit0 = part * units_per_part;
-                const uint32_t piece0 = unit0 >> 4, w0 = units_per_part >= 16u ? 0u : unit0 & 15u;
-                const uint32_t n_pieces_here = units_per_part >= 16u ? units_per_part >> 4 : 1u;
-                const uint32_t w_end = units_per_part >= 16u ? n_words : w0 + units_per_part;
                 uint32_t Sp[NW], Y[NW], tagp = 0;       // the parent's representative, its first update
 #pragma unroll
                 for (int w = 0; w < NW; ++w) { Sp[w] = 0; Y[w] = 0; }
@@ -517,64 +498,14 @@ __global__ __launch_bounds__(kPoolBlock, pool_min_waves(NW)) void k_attract_pool
                     uint32_t d = 0;
 #pragma unroll
                     for (int w = 0; w < NW; ++w) d |= (e[w] ^ Y[w]) & indep[w];
-                    const bool ok = lv && d == 0;
+                    bool ok = lv && d == 0;
                     if (!__ballot(ok)) continue;
-                    // the children whose first update is exactly this cycle state: dependent nodes, 32 children per word
-                    uint32_t n_hit = 0;
-                    for (uint32_t piece = piece0; piece < piece0 + n_pieces_here; ++piece) {
-                        uint32_t match[16];
-#pragma unroll
-                        for (int w = 0; w < 16; ++w) match[w] = ((uint32_t)w >= w0 && (uint32_t)w < w_end) ? word_mask : 0u;
-                        for (uint32_t di = 0; di < n_dep; ++di) {
-                            LeafDep dep;                                        // uniform (one broadcast read)
-                            {
-                                const uint32_t* const dw = dep_lds + 4u * di;
-                                const uint32_t d0w = __builtin_amdgcn_readfirstlane(dw[0]), d1w = __builtin_amdgcn_readfirstlane(dw[1]);
-                                const uint32_t d2w = __builtin_amdgcn_readfirstlane(dw[2]);
-                                dep.in[0] = (uint16_t)d0w; dep.in[1] = (uint16_t)(d0w >> 16); dep.in[2] = (uint16_t)d1w; dep.in[3] = (uint16_t)(d1w >> 16);
-                                dep.node = (uint16_t)d2w; dep.k = (uint16_t)(d2w >> 16);
-                                dep.tt = __builtin_amdgcn_readfirstlane(dw[3]);
-                            }
-                            const uint32_t node = dep.node, k = dep.k;
-                            uint32_t want_bit = 0;                              // this cycle state's value of the node (uniform)
-#pragma unroll
-                            for (int w = 0; w < NW; ++w) want_bit |= e[w] & (((node >> 5) == (uint32_t)w) ? 1u << (node & 31u) : 0u);
-                            const uint32_t want = want_bit ? 0xFFFFFFFFu : 0u;
-                            uint32_t selp[kLeafMaxK];                           // inputs that are parent bits: one broadcast per lane
-#pragma unroll
-                            for (int j = 0; j < (int)kLeafMaxK; ++j)
-                                selp[j] = ((uint32_t)j < k && !(dep.in[j] & 0x8000u)) ? 0u - get_bit<NW>(Sp, dep.in[j]) : 0u;
-#pragma unroll
-                            for (int w = 0; w < 16; ++w) {
-                                if ((uint32_t)w >= w0 && (uint32_t)w < w_end) { // uniform
-                                    const uint32_t wg = piece * 16u + (uint32_t)w;     // the word's number among all children's
-                                    uint32_t sel[kLeafMaxK];
-#pragma unroll
-                                    for (int j = 0; j < (int)kLeafMaxK; ++j) {
-                                        const uint32_t q_digit = dep.in[j] & 0x7FFFu;
-                                        const uint32_t pat = q_digit == 0u ? 0xAAAAAAAAu : q_digit == 1u ? 0xCCCCCCCCu : q_digit == 2u ? 0xF0F0F0F0u :
-                                                             q_digit == 3u ? 0xFF00FF00u : q_digit == 4u ? 0xFFFF0000u :
-                                                             (((wg >> (q_digit - 5u)) & 1u) ? 0xFFFFFFFFu : 0u);
-                                        sel[j] = (dep.in[j] & 0x8000u) ? pat : selp[j];
-                                    }
-                                    // mux tree over the table bits (inputs beyond k select the low half: their selector is 0)
-                                    uint32_t v[1 << (kLeafMaxK - 1)];
-#pragma unroll
-                                    for (int i = 0; i < (1 << (kLeafMaxK - 1)); ++i) {
-                                        const uint32_t lo = 0u - ((dep.tt >> (2 * i)) & 1u), hi = 0u - ((dep.tt >> (2 * i + 1)) & 1u);
-                                        v[i] = (sel[0] & hi) | (~sel[0] & lo);
-                                    }
-#pragma unroll
-                                    for (int j = 1; j < (int)kLeafMaxK; ++j)
-#pragma unroll
-                                        for (int i = 0; i < (1 << (kLeafMaxK - 1 - j)); ++i) v[i] = bfi(sel[j], v[2 * i + 1], v[2 * i]);
-                                    match[w] &= ~(v[0] ^ want);
-                                }
-                            }
-                        }
-#pragma unroll
-                        for (int w = 0; w < 16; ++w) n_hit += (uint32_t)__popc(match[w]);
-                    }
+                    // the children whose first update is exactly this cycle state: the free digits' factor (none: no child
+                    // of this parent hits), then the entangled digits' assignments, 32 per word
+                    const uint32_t shift = leaf_free_shift<NW>(Sp, e, dep_lds, n_enum, n_free, kb, m);
+                    ok = ok && shift != kLeafNoChild;
+                    if (!__ballot(ok)) continue;
+                    uint32_t n_hit = leaf_enum_hits<NW>(Sp, e, dep_lds, n_enum, m, part, parts) << (shift & 31u);
                     n_hit = ok ? n_hit : 0u;
                     if (n_hit) atomicAdd(&wave_cnt[2u * ((tagw & kTagMask) - 1u)], n_hit);
                     hits += n_hit;
