@@ -23,7 +23,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 EXPORTS = (
     'bsx_create', 'bsx_destroy', 'bsx_last_error', 'bsx_status_string', 'bsx_device_info', 'bsx_network_info',
     'bsx_set_network', 'bsx_set_problem_space', 'bsx_run_attract', 'bsx_run_attract2', 'bsx_run_attract_wide', 'bsx_run_attract_fgraph', 'bsx_run_target',
-    'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_run_attractor_profile', 'bsx_run_node_correlations', 'bsx_run_attractor_transitions',
+    'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_run_attractor_profile', 'bsx_run_node_correlations', 'bsx_run_attractor_transitions', 'bsx_run_attractor_transitions_wide',
     'bsx_synchronize',
     'bsx_comm_unique_id', 'bsx_comm_init', 'bsx_comm_allgather', 'bsx_comm_destroy',
 )
@@ -156,6 +156,7 @@ def load():
     lib.bsx_run_attractor_profile.argtypes = [vp, vp, u32, vp, u64, vp, vp, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_node_correlations.argtypes = [vp, vp, u32, vp, vp, u64, vp, vp, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_attractor_transitions.argtypes = [vp, vp, u32, vp, u64, u64, vp, u64, C.POINTER(u64), vp, vp, C.POINTER(Stats)]
+    lib.bsx_run_attractor_transitions_wide.argtypes = lib.bsx_run_attractor_transitions.argtypes
     lib.bsx_synchronize.argtypes = [vp]
     lib.bsx_comm_unique_id.argtypes = [vp, vp, u32]
     lib.bsx_comm_init.argtypes = [vp, vp, u32, C.c_int, C.c_int]

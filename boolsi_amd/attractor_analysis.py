@@ -110,12 +110,11 @@ def attractor_transitions(engine, attractors, max_t=inf):
     once and the network followed until it is on a cycle again.
     -> (edges, n_free): the engine's edge records (src and dst index `attractors`; dst may be _lib.TRANS_OUTSIDE or
     _lib.TRANS_UNRESOLVED) and the number of free nodes, so that attractor q has length_q * n_free flips.
-    None on the wide-state family, which the device call does not support.
+    Networks on the wide-state family go through Engine.attractor_transitions_wide.
     """
-    if engine.wide:
-        return None
-    edges, _, closed = engine.attractor_transitions([a.key for a in attractors], [a.length for a in attractors], max_t=max_t,
-                                                    edge_cap=max(1, min(1 << 24, len(attractors) * (len(attractors) + 2))))
+    call = engine.attractor_transitions_wide if engine.wide else engine.attractor_transitions
+    edges, _, closed = call([a.key for a in attractors], [a.length for a in attractors], max_t=max_t,
+                            edge_cap=max(1, min(1 << 24, len(attractors) * (len(attractors) + 2))))
     for a, ok in zip(attractors, closed):
         if not ok:
             raise RuntimeError('attractor {} does not return to its key state after {} steps'.format(a.key, a.length))

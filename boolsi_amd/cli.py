@@ -212,11 +212,8 @@ def attract(**kw):
         if kw['transitions']:
             from .attractor_analysis import attractor_transitions
             from .output import output_attractor_transitions
-            found = attractor_transitions(engine, attractors, max_t)
-            if found is None:
-                logging.getLogger().info('Attractor transitions are not available for networks of more than 256 nodes.')
-            else:
-                output_attractor_transitions(found[0], [a.length for a in attractors], found[1], run.out)
+            edges, n_free = attractor_transitions(engine, attractors, max_t)
+            output_attractor_transitions(edges, [a.length for a in attractors], n_free, run.out)
     _guarded(kw, body)
 
 

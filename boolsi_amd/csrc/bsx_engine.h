@@ -179,7 +179,7 @@ int wide_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, ui
                         uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats);
 int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
                      uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
-                     uint64_t sum_len, bsx_stats* stats, DevBuf<uint32_t>* keep_on);
+                     uint64_t sum_len, bsx_stats* stats, DevBuf<uint32_t>* keep_on, ProfileKeep* keep_states = nullptr);
 // bsx_profile_api.cpp: the checks and the per-lane family of bsx_run_attractor_profile, shared with
 // bsx_run_node_correlations (bsx_corr_api.cpp), which keeps the on-counts on the device (keep_on), and with
 // bsx_run_attractor_transitions (bsx_trans_api.cpp), which keeps the states there (keep_states)

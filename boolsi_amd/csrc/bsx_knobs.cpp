@@ -47,6 +47,7 @@ Knobs Knobs::from_env() {
     if (const char* e = std::getenv("BSX_CORR_BATCH_CELLS")) k.corr_batch_cells = std::strtoull(e, nullptr, 10);
     k.trans_step_limit = kStepLimit;
     if (const char* e = std::getenv("BSX_TRANS_STEP_LIMIT")) k.trans_step_limit = std::max(1u, std::min(kStepLimit, (uint32_t)std::atoi(e)));
+    if (const char* e = std::getenv("BSX_WTRANS_CHUNK")) k.wtrans_chunk = std::max(1ull, std::strtoull(e, nullptr, 10));
     return k;
 }
 

@@ -38,6 +38,7 @@ struct Knobs {
     uint32_t wide_step_limit = 0;   // BSX_WIDE_STEP_LIMIT: 16 .. kWideStepLimit (default: kWideStepLimit)
     uint64_t corr_batch_cells = 0;  // BSX_CORR_BATCH_CELLS: cells (columns x attractors) per sort batch of the node correlations (0 = not set)
     uint32_t trans_step_limit = 0;  // BSX_TRANS_STEP_LIMIT: 1 .. kStepLimit, per walk of the attractor transitions (default: kStepLimit)
+    uint64_t wtrans_chunk = 0;      // BSX_WTRANS_CHUNK: flips per launch of the wide attractor transitions, at least 1 (0 = not set)
 
     static Knobs from_env();
 };

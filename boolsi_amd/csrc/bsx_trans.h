@@ -36,7 +36,7 @@ struct alignas(8) TransCtr {            // zeroed (open_row / dup_row: all ones)
     unsigned int probe_full;            // k_trans_build: a probe went round the whole table (cannot happen at load <= 1/2)
     unsigned int step_limit_hits;       // walks undecided at the step limit
     unsigned int edge_overflow;         // the HBM edge table was full
-    unsigned int pad;
+    unsigned int rows_undecided;        // wide family: closed rows whose own walk ran into the step limit (else unused)
     unsigned long long n_edges;         // k_trans_drain's cursor
     unsigned long long steps_exec;      // network updates of the walk kernel
 };

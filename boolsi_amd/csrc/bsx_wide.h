@@ -86,6 +86,46 @@ inline uint32_t wide_profile_lds_words(uint32_t rows, uint32_t L, uint32_t n_fsl
     return 2 * rows * L + 2 * n_fslots * L + kWideThreads + 2 * L + 32 * L + 8;
 }
 
+// ---- attractor transitions (k_wide_trans / k_wide_trans_build in bsx_wide.hip, bsx_run_attractor_transitions_wide) ----
+// A group of 32 * L trajectories runs k_wide's attract phases (Brent in lock step, the mu pass, the key lap) with
+// T_p = 0 and the origin's fixed nodes only.  Two kinds of source:
+//   rows   trajectory k starts at the key of row first + k (rows whose profile `closed` flag is 0 are not walked);
+//          per row the true period, mu and the canonical key (the cycle's minimum state) are written;
+//   flips  flip f = first + k is (listed state f / n_free, free node f % n_free): that state with one bit inverted;
+//          the flip's canonical key is looked up in the table of the rows' keys (bsx_wtrans.h) and the edge
+//          accumulated, per group in LDS first and then in the HBM edge table of bsx_trans.h.
+// `net` carries the network part of WideParams and max_t / cap_inf / step_limit / x0; nothing of a problem space.
+struct TransEdgeSlot;
+struct TransCtr;
+enum WideTransStage : uint32_t { kWideTransRows = 0, kWideTransFlips = 1 };
+struct WideTransParams {
+    WideParams net;
+    uint32_t stage;
+    uint32_t key_stride;            // uint64 words per row of `keys` (>= w64)
+    uint64_t first, count;          // this launch: rows / flips [first, first + count)
+    uint64_t n_rows;
+    const uint64_t* keys;           // [n_rows][key_stride]
+    const uint64_t* lengths;        // [n_rows]
+    const uint8_t* closed;          // [n_rows], from the profile
+    const uint64_t* states;         // [sum of the lengths][w64], row after row, from the profile
+    const uint64_t* row_first;      // [n_rows] index of a row's first state
+    const uint32_t* free_nodes;     // [n_free] ascending
+    uint32_t n_free, pad;
+    uint32_t* row_info;             // [n_rows][2] true period (0: not walked or undecided), mu
+    uint64_t* row_keys;             // [n_rows][w64] canonical keys
+    uint32_t* owners;               // row-key table: [slot_mask + 1], row + 1, 0 = free
+    uint64_t slot_mask;
+    TransEdgeSlot* edges;           // HBM edge table
+    uint64_t edge_mask;             // its slots - 1
+    uint32_t* node_exits;           // nullable: [n_rows][n_nodes]
+    TransCtr* ctr;
+};
+// LDS words of k_wide_trans: k_wide's layout without perturbation variations (never more than wide_lds_words gives
+// for the L that wide_set_problem_space chose); the group's edge table lies in the first matrix, dead by then.
+inline uint32_t wide_trans_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslots) {
+    return kWideBuffers * rows * L + 2 * n_fslots * L + 2 * kWideThreads + 8 * L + 4 * 32 * L + 8;
+}
+
 // ---- device-side reduction of the kernel's per-problem records (bsx_wide_reduce.hip) ----
 // Attract: an open-addressing HBM table keyed by the whole w64-word key, linear probing.
 // Widths of the sums, for at most 2^64 - 1 problems per call (bsx_run_attract_wide refuses more) and

@@ -13,7 +13,9 @@
 
 #include "bsx_device.h"
 #include "bsx_planes.h"
+#include "bsx_trans.h"
 #include "bsx_wide.h"
+#include "bsx_wtrans.h"
 
 namespace bsx {
 
@@ -706,6 +708,366 @@ hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, c
         case 6: return launch_wide_profile_k<6>(grid, shmem, st, Q);
         default: return hipErrorInvalidValue;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Attractor transitions (bsx_run_attractor_transitions_wide; bsx_wide.h has the stages, bsx_wtrans.h the lookup and
+// the classification).  The walk is k_wide's attract branch with T_p = 0, no schedule and no variations.
+namespace {
+
+// Deposits the 64-bit state words src(k, w) of the group's trajectories k into matrix `dst` (rows this thread owns,
+// as wide_key_rows): bit b of dst[r][c] = node r of trajectory 32 c + b.
+template <typename F>
+__device__ __forceinline__ void wide_trans_deposit(const WideParams& P, const WideCtx& X, uint32_t* dst, F src) {
+    uint64_t kw[32];
+    uint32_t have = kWideNone;
+    for (uint32_t r = X.r0; r < X.r1; ++r) {
+        if ((r >> 6) != have) {
+            have = r >> 6;
+#pragma unroll
+            for (int b = 0; b < 32; ++b) kw[b] = have < P.w64 ? src(32u * X.c + (uint32_t)b, have) : 0ull;
+        }
+        uint32_t word = 0;
+#pragma unroll
+        for (int b = 0; b < 32; ++b) word |= (uint32_t)((kw[b] >> (r & 63u)) & 1ull) << b;
+        dst[r * X.L + X.c] = r < P.n_nodes ? word : 0u;
+    }
+}
+
+// largest q with row_first[q] <= g  (row_first ascending, row_first[0] == 0)
+__device__ __forceinline__ uint32_t wide_trans_row_of(const uint64_t* row_first, uint64_t n_rows, uint64_t g) {
+    uint64_t lo = 0, hi = n_rows;
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (row_first[mid] <= g) lo = mid; else hi = mid;
+    }
+    return (uint32_t)lo;
+}
+
+// Insert-or-add into the HBM edge table (as trans_edge_global of bsx_trans_kernel.h): the key word is claimed by one
+// 64-bit CAS; count and sum take atomic adds.  At most one round of the table.
+__device__ __forceinline__ void wide_trans_edge_global(const WideTransParams& Q, unsigned long long key, unsigned long long count,
+                                                       unsigned long long sum_mu) {
+    uint64_t at = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) & Q.edge_mask;
+    for (uint64_t probe = 0; probe <= Q.edge_mask; ++probe, at = (at + 1) & Q.edge_mask) {
+        TransEdgeSlot* slot = Q.edges + at;
+        unsigned long long seen = __hip_atomic_load(&slot->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (seen == 0) seen = atomicCAS(&slot->key, 0ull, key);
+        if (seen == 0 || seen == key) {
+            atomicAdd(&slot->count, count);
+            if (sum_mu) atomicAdd(&slot->sum_mu, sum_mu);
+            return;
+        }
+    }
+    atomicAdd(&Q.ctr->edge_overflow, 1u);
+}
+
+}  // namespace
+
+template <int K, bool KW>
+__global__ __launch_bounds__(kWideThreads) void k_wide_trans(const WideTransParams Q) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
+    const WideParams& P = Q.net;
+    const bool flips = Q.stage == kWideTransFlips;
+    // refused tables (a row that is not closed or undecided, two rows on one cycle) are known on the device only: the
+    // launches before this one left them in the counters, and no flip is walked
+    if (flips && (Q.ctr->open_row != kTransNoRow || Q.ctr->dup_row != kTransNoRow || Q.ctr->probe_full || Q.ctr->rows_undecided)) return;
+    WideCtx X;
+    X.L = P.L;
+    X.tid = threadIdx.x;
+    X.c = X.tid & (P.L - 1);
+    X.slice = X.tid >> P.lshift;
+    X.r0 = X.slice * P.rows_ps;
+    X.r1 = X.r0 + P.rows_ps;
+    X.RL = P.rows * P.L;
+    const uint32_t L = P.L, c = X.c, RL = X.RL, G = 32 * L, tid = X.tid;
+    const uint32_t nslices = kWideThreads / L;
+    uint32_t* B[4] = {sm, sm + RL, sm + 2 * RL, sm + 3 * RL};
+    uint32_t* fmv = sm + 4 * RL;                    // [n_fslots][2][L]  all zero: no variations here
+    uint32_t* red = fmv + 2 * P.n_fslots * L;       // [2][256]          per-thread partials
+    uint32_t* col = red + 2 * kWideThreads;         // [8][L]            per-column masks
+    uint32_t* src = col + 8 * L;                    // [G] flips: index of the listed state
+    uint32_t* lam = src + G;                        // [G] lambda
+    uint32_t* mua = lam + G;                        // [G] mu (while the group is set up: the flipped node)
+    uint32_t* sta = mua + G;                        // [G] state of the trajectory's search
+    uint32_t* misc = sta + G;                       // [8]
+    enum : uint32_t { ST_ACTIVE = 0, ST_CAND = 1, ST_FOUND = 2, ST_NONE = 3, ST_INVALID = 4 };
+    unsigned long long steps_exec = 0;
+    unsigned int limit_hits = 0;
+    for (uint32_t i = tid; i < 2 * P.n_fslots * L; i += kWideThreads) fmv[i] = 0;
+    // found iff mu + lambda <= max_t; a max_t at or beyond a quarter of the step limit counts as unbounded (k_wide), and
+    // the rows' own walks are never capped
+    const uint64_t cap = (!flips || P.cap_inf || P.max_t >= P.step_limit / 4) ? ~0ull : P.max_t;
+
+    const uint64_t n_groups = (Q.count + G - 1) / G;
+    for (uint64_t group = blockIdx.x; group < n_groups; group += gridDim.x) {
+        const uint64_t base = group * G;
+        const uint32_t n_valid = (uint32_t)((Q.count - base) < G ? (Q.count - base) : G);
+        if (tid < 8) misc[tid] = 0;
+        for (uint32_t k = tid; k < G; k += kWideThreads) {
+            uint32_t st = ST_INVALID, g = 0, node = 0;
+            if (k < n_valid) {
+                const uint64_t id = Q.first + base + k;
+                if (flips) {
+                    const uint64_t s = id / Q.n_free;
+                    g = (uint32_t)s;                                    // (< BSX_TRANS_MAX_STATES)
+                    node = Q.free_nodes[(uint32_t)(id - s * Q.n_free)];
+                    st = ST_ACTIVE;
+                } else if (Q.closed[id]) {
+                    st = ST_ACTIVE;
+                }
+            }
+            src[k] = g; mua[k] = node; sta[k] = st; lam[k] = 0;
+        }
+        __syncthreads();
+        // ---- x_0: a row's key, or a listed state with one bit inverted
+        wide_trans_deposit(P, X, B[0], [&](uint32_t k, uint32_t w) -> uint64_t {
+            if (sta[k] != ST_ACTIVE) return 0ull;
+            if (!flips) return Q.keys[(Q.first + base + k) * Q.key_stride + w];
+            const uint64_t word = Q.states[(uint64_t)src[k] * P.w64 + w];
+            return (mua[k] >> 6) == w ? word ^ (1ull << (mua[k] & 63u)) : word;
+        });
+        __syncthreads();
+        for (uint32_t k = tid; k < G; k += kWideThreads) mua[k] = 0;
+        uint32_t* cur = B[0];
+        uint32_t* nxt = B[1];
+        uint64_t group_steps = 0;
+        uint32_t* x0 = P.x0 + (size_t)blockIdx.x * RL;
+        for (uint32_t r = X.r0; r < X.r1; ++r) x0[r * L + c] = cur[r * L + c];
+        // ---- Brent's detector in lock step; the tortoise lives in B[2]
+        {
+            uint32_t* T = B[2];
+            for (uint32_t r = X.r0; r < X.r1; ++r) T[r * L + c] = cur[r * L + c];
+            uint64_t tau = 0, power = 1, lamc = 0;
+            for (;;) {
+                bool left = false;
+                if (tid < L)
+                    for (uint32_t b = 0; b < 32; ++b) left = left || sta[32 * tid + b] == ST_ACTIVE;
+                if (!__syncthreads_or(left)) break;
+                wide_step<K, KW>(P, X, cur, nxt, fmv, 0xFFFFFFFFu);
+                ++tau; ++lamc; ++group_steps;
+                const bool tele = lamc == power;
+                uint32_t diff = 0;
+                for (uint32_t r = X.r0; r < X.r1; ++r) {          // (own rows only: no barrier between write and read)
+                    const uint32_t v = nxt[r * L + c];
+                    diff |= v ^ T[r * L + c];
+                    if (tele) T[r * L + c] = v;
+                }
+                red[tid] = diff;
+                __syncthreads();
+                if (tid < L) {
+                    uint32_t df = 0;
+                    for (uint32_t s = 0; s < nslices; ++s) df |= red[s * L + tid];
+                    for (uint32_t b = 0; b < 32; ++b) {
+                        const uint32_t k = 32 * tid + b;
+                        if (sta[k] != ST_ACTIVE) continue;
+                        if (!((df >> b) & 1u)) {
+                            lam[k] = (uint32_t)lamc;
+                            sta[k] = (uint64_t)lamc > cap ? ST_NONE : ST_CAND;
+                        } else if (cap == ~0ull ? tau >= P.step_limit : tau >= 3 * cap + 2) {
+                            sta[k] = ST_NONE;
+                            if (cap == ~0ull) ++limit_hits;
+                        }
+                    }
+                }
+                if (tele) { power <<= 1; lamc = 0; }
+                uint32_t* s = cur; cur = nxt; nxt = s;
+            }
+        }
+        // ---- mu: y = s(lambda) (bit b frozen after lambda_b steps) in B[0] / B[1], x = s(0) in B[2] / B[3]
+        if (tid == 0) misc[2] = 0;
+        __syncthreads();
+        if (tid < L)
+            for (uint32_t b = 0; b < 32; ++b)
+                if (sta[32 * tid + b] == ST_CAND) atomicMax(&misc[2], lam[32 * tid + b]);
+        __syncthreads();
+        const uint32_t lam_max = misc[2];
+        uint32_t* mn = B[2];
+        if (lam_max) {
+            uint32_t* ya = B[0]; uint32_t* yb = B[1];
+            uint32_t* xa = B[2]; uint32_t* xb = B[3];
+            for (uint32_t r = X.r0; r < X.r1; ++r) { ya[r * L + c] = x0[r * L + c]; xa[r * L + c] = x0[r * L + c]; }
+            for (uint32_t m = 0; m < lam_max; ++m) {
+                if (tid < L) {
+                    uint32_t act = 0;
+                    for (uint32_t b = 0; b < 32; ++b) act |= (m < lam[32 * tid + b] ? 1u : 0u) << b;
+                    col[tid] = act;
+                }
+                __syncthreads();
+                wide_step<K, KW>(P, X, ya, yb, fmv, col[c]);
+                __syncthreads();
+                uint32_t* s = ya; ya = yb; yb = s;
+                ++group_steps;
+            }
+            for (uint64_t m = 0;; ++m) {
+                uint32_t diff = 0;
+                for (uint32_t r = X.r0; r < X.r1; ++r) diff |= ya[r * L + c] ^ xa[r * L + c];
+                red[tid] = diff;
+                __syncthreads();
+                bool left = false;
+                if (tid < L) {
+                    uint32_t df = 0;
+                    for (uint32_t s = 0; s < nslices; ++s) df |= red[s * L + tid];
+                    for (uint32_t b = 0; b < 32; ++b) {
+                        const uint32_t k = 32 * tid + b;
+                        if (sta[k] != ST_CAND) continue;
+                        if (!((df >> b) & 1u)) {
+                            mua[k] = (uint32_t)m;
+                            sta[k] = ST_FOUND;
+                        } else if (m + 1 + lam[k] > cap) {
+                            sta[k] = ST_NONE;
+                        } else if (m >= P.step_limit) {
+                            sta[k] = ST_NONE;
+                            ++limit_hits;
+                        } else {
+                            left = true;
+                        }
+                    }
+                }
+                if (!__syncthreads_or(left)) break;
+                wide_step<K, KW>(P, X, ya, yb, fmv, 0xFFFFFFFFu);
+                wide_step<K, KW>(P, X, xa, xb, fmv, 0xFFFFFFFFu);
+                __syncthreads();
+                uint32_t* s = ya; ya = yb; yb = s;
+                s = xa; xa = xb; xb = s;
+                group_steps += 2;
+            }
+            // ---- key: minimum over a lap of lam_max steps from y (on the cycle of every found bit), min in xa
+            cur = ya; nxt = yb;
+            mn = xa;
+            for (uint32_t r = X.r0; r < X.r1; ++r) mn[r * L + c] = cur[r * L + c];
+            for (uint32_t m = 1; m < lam_max; ++m) {
+                wide_step<K, KW>(P, X, cur, nxt, fmv, 0xFFFFFFFFu);
+                __syncthreads();
+                uint32_t* s = cur; cur = nxt; nxt = s;
+                ++group_steps;
+                uint32_t lt = 0, eq = 0xFFFFFFFFu;
+                for (uint32_t r = X.r1; r-- > X.r0;) {
+                    const uint32_t v = cur[r * L + c], w = mn[r * L + c];
+                    lt |= eq & ~v & w;
+                    eq &= ~(v ^ w);
+                }
+                red[tid] = lt;
+                red[kWideThreads + tid] = eq;
+                __syncthreads();
+                if (tid < L) {
+                    uint32_t LT = 0, EQ = 0xFFFFFFFFu;
+                    for (uint32_t s2 = nslices; s2-- > 0;) {
+                        LT |= EQ & red[s2 * L + tid];
+                        EQ &= red[kWideThreads + s2 * L + tid];
+                    }
+                    col[L + tid] = LT;
+                }
+                __syncthreads();
+                const uint32_t sel = col[L + c];
+                for (uint32_t r = X.r0; r < X.r1; ++r) mn[r * L + c] = wbfi(sel, cur[r * L + c], mn[r * L + c]);
+            }
+        }
+        __syncthreads();
+        if (!flips) {
+            // ---- per row: true period, mu, canonical key
+            for (uint32_t k = tid; k < n_valid; k += kWideThreads) {
+                const uint64_t q = Q.first + base + k;
+                const bool found = sta[k] == ST_FOUND;
+                Q.row_info[2 * q + 0] = found ? lam[k] : 0u;
+                Q.row_info[2 * q + 1] = found ? mua[k] : 0u;
+                for (uint32_t w = 0; w < P.w64; ++w) Q.row_keys[q * P.w64 + w] = found ? wide_gather64(P, mn, L, k, w) : 0ull;
+            }
+        } else {
+            // ---- per flip: the key among the rows' keys, the edge; the group's edges meet in LDS first (in the first
+            //      matrix: the minimum lies in the third or fourth, nothing else is read any more)
+            TransEdgeSlot* lds_edges = reinterpret_cast<TransEdgeSlot*>(B[0]);
+            for (uint32_t e = tid; e < kTransLdsEdges; e += kWideThreads) lds_edges[e] = TransEdgeSlot{0ull, 0ull, 0ull};
+            __syncthreads();
+            for (uint32_t k = tid; k < n_valid; k += kWideThreads) {
+                const uint64_t f = Q.first + base + k;
+                const uint32_t node = Q.free_nodes[(uint32_t)(f - (uint64_t)src[k] * Q.n_free)];
+                const uint32_t q = wide_trans_row_of(Q.row_first, Q.n_rows, src[k]);
+                const bool found = sta[k] == ST_FOUND;
+                uint32_t row = kWtransNoRow;
+                if (found)
+                    row = wtrans_find_of(Q.owners, Q.slot_mask, Q.row_keys, P.w64, [&](uint32_t w) { return wide_gather64(P, mn, L, k, w); });
+                const WtransEdge edge = wtrans_classify(found, lam[k], mua[k], row, P.cap_inf ? kWtransInf : P.max_t);
+                if (Q.node_exits && edge.dst != q) atomicAdd(&Q.node_exits[(uint64_t)q * P.n_nodes + node], 1u);
+                const unsigned long long key = (((unsigned long long)q << 32) | edge.dst) + 1ull;
+                uint32_t at = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) & (kTransLdsEdges - 1);
+                bool placed = false;
+                for (uint32_t probe = 0; probe < kTransLdsProbes && !placed; ++probe, at = (at + 1) & (kTransLdsEdges - 1)) {
+                    unsigned long long seen = lds_edges[at].key;
+                    if (seen == 0) seen = atomicCAS(&lds_edges[at].key, 0ull, key);
+                    if (seen == 0 || seen == key) {
+                        atomicAdd(&lds_edges[at].count, 1ull);
+                        if (edge.mu) atomicAdd(&lds_edges[at].sum_mu, (unsigned long long)edge.mu);
+                        placed = true;
+                    }
+                }
+                if (!placed) wide_trans_edge_global(Q, key, 1ull, edge.mu);
+            }
+            __syncthreads();
+            for (uint32_t e = tid; e < kTransLdsEdges; e += kWideThreads)
+                if (lds_edges[e].key) wide_trans_edge_global(Q, lds_edges[e].key, lds_edges[e].count, lds_edges[e].sum_mu);
+        }
+        steps_exec += group_steps * n_valid;
+        __syncthreads();
+    }
+    if (tid == 0 && steps_exec) atomicAdd(&Q.ctr->steps_exec, steps_exec);
+    if (limit_hits) atomicAdd(&Q.ctr->step_limit_hits, limit_hits);
+}
+
+// One thread per row, behind the rows' walks: a row that is not closed (or not a whole number of its periods) is an
+// open row; a length that is a proper multiple of the period repeats its own states; every other row claims a slot of
+// the row-key table for its canonical key.  On an occupied slot the two keys are compared in row_keys, which the launch
+// before this one wrote: nothing is half-visible, nothing spins.  Equal keys are two rows on one cycle: the later one
+// is named.
+__global__ __launch_bounds__(256) void k_wide_trans_build(const WideTransParams Q) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= Q.n_rows) return;
+    const uint32_t w64 = Q.net.w64;
+    if (!Q.closed[q]) { atomicMin(&Q.ctr->open_row, (unsigned int)q); return; }
+    const uint32_t period = Q.row_info[2 * q], mu = Q.row_info[2 * q + 1];
+    if (period == 0) { atomicAdd(&Q.ctr->rows_undecided, 1u); return; }        // (its walk ran into the step limit)
+    const uint64_t length = Q.lengths[q];
+    if (mu != 0 || length % period != 0) { atomicMin(&Q.ctr->open_row, (unsigned int)q); return; }
+    if (length != period) { atomicMin(&Q.ctr->dup_row, (unsigned int)q); return; }
+    const uint64_t* mine = Q.row_keys + q * w64;
+    uint64_t at = wtrans_hash(mine, w64) & Q.slot_mask;
+    for (uint64_t probe = 0; probe <= Q.slot_mask; ++probe, at = (at + 1) & Q.slot_mask) {
+        const uint32_t owner = atomicCAS(&Q.owners[at], 0u, (uint32_t)q + 1u);
+        if (owner == 0) return;
+        if (wtrans_key_equal(mine, Q.row_keys + (uint64_t)(owner - 1) * w64, w64)) {
+            const uint32_t other = owner - 1;
+            atomicMin(&Q.ctr->dup_row, (uint32_t)q > other ? (uint32_t)q : other);
+            return;
+        }
+    }
+    atomicAdd(&Q.ctr->probe_full, 1u);
+}
+
+template <int K>
+static hipError_t launch_wide_trans_k(dim3 grid, size_t shmem, hipStream_t st, const WideTransParams& Q) {
+    const void* fn = Q.net.wdesc ? (const void*)k_wide_trans<K, true> : (const void*)k_wide_trans<K, false>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return e;
+    void* args[] = {const_cast<WideTransParams*>(&Q)};
+    return hipLaunchKernel(fn, grid, dim3(kWideThreads), args, shmem, st);
+}
+
+hipError_t launch_wide_trans(int k, dim3 grid, size_t shmem, hipStream_t st, const WideTransParams& Q) {
+    switch (k) {
+        case 1: return launch_wide_trans_k<1>(grid, shmem, st, Q);
+        case 2: return launch_wide_trans_k<2>(grid, shmem, st, Q);
+        case 3: return launch_wide_trans_k<3>(grid, shmem, st, Q);
+        case 4: return launch_wide_trans_k<4>(grid, shmem, st, Q);
+        case 5: return launch_wide_trans_k<5>(grid, shmem, st, Q);
+        case 6: return launch_wide_trans_k<6>(grid, shmem, st, Q);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_wide_trans_build(const WideTransParams& Q, hipStream_t st) {
+    const uint64_t blocks = (Q.n_rows + 255) / 256;
+    hipLaunchKernelGGL(k_wide_trans_build, dim3((uint32_t)blocks), dim3(256), 0, st, Q);
+    return hipGetLastError();
 }
 
 }  // namespace bsx

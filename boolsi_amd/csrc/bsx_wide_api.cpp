@@ -9,12 +9,16 @@
 
 #include "bsx_engine.h"
 #include "bsx_host.h"
+#include "bsx_trans.h"
 #include "bsx_wide.h"
+#include "bsx_wtrans.h"
 
 namespace bsx {
 
 hipError_t launch_wide(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& P);
 hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, const WideProfileParams& Q);
+hipError_t launch_wide_trans(int k, dim3 grid, size_t shmem, hipStream_t st, const WideTransParams& Q);
+hipError_t launch_wide_trans_build(const WideTransParams& Q, hipStream_t st);
 hipError_t launch_wide_reduce_attract(const uint32_t* info, const uint64_t* keys, uint64_t m, uint32_t w64, WideSlot* table,
                                       uint64_t slots, unsigned long long* hdr, hipStream_t st);
 hipError_t launch_wide_reduce_drain(const WideSlot* table, uint64_t slots, WideAttrRec* out, uint64_t cap, unsigned long long* hdr,
@@ -40,6 +44,7 @@ struct WideHost {
     // problem space
     bool have_space = false;
     uint32_t origin[kWideMaxW32] = {};
+    uint32_t fixmask[kWideMaxW32] = {};     // nodes the origin fixes (constant rules in the descriptors)
     uint32_t n_any = 0, n_fv = 0, n_pv = 0, n_sched = 0, n_fslots = 0, tp_origin = 0;
     uint32_t L = 0;
     size_t shmem = 0;
@@ -142,6 +147,9 @@ int wide_set_problem_space(bsx_handle h, const uint64_t* origin_state_words, con
         if (fixed[j].node >= n || fixed[j].value > 1) return fail(h, BSX_ERR_INVALID, "bad fixed node entry");
         fixed_val[fixed[j].node] = (int)fixed[j].value;
     }
+    std::memset(W.fixmask, 0, sizeof(W.fixmask));
+    for (uint32_t i = 0; i < n; ++i)
+        if (fixed_val[i] >= 0) W.fixmask[i >> 5] |= 1u << (i & 31);
     std::vector<uint32_t> fv, pv;
     uint32_t n_slots = 0;
     for (uint32_t j = 0; j < n_fixed_var; ++j) {
@@ -335,24 +343,30 @@ int wide_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* 
 
 // bsx_run_attractor_profile on the wide family (bsx_profile_api.cpp has checked every argument): one k_wide_profile
 // launch per BSX_PROFILE_CHUNK_WIDE attractors, all enqueued before the one wait.
+// keep_states (as profile_lanes): states and closure are written whether or not the caller wants them on the host and
+// every device buffer of the call stays in *keep_states; the launches are enqueued and NOT waited for, nothing is
+// copied back and `stats` is not written (the wide attractor transitions go on enqueueing behind them).
 int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
                      uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
-                     uint64_t sum_len, bsx_stats* stats, DevBuf<uint32_t>* keep_on) {
+                     uint64_t sum_len, bsx_stats* stats, DevBuf<uint32_t>* keep_on, ProfileKeep* keep_states) {
     static_assert(BSX_PROFILE_CHUNK_WIDE % (32 * 64) == 0, "a chunk is whole groups for every L");
     const double t_begin = now_ms();
     WideHost& W = *h->wide;
     if (W.rows / (kWideThreads / W.L) > kWideProfileRows)      // (before any device work, as every check of this call)
         return fail(h, BSX_ERR_UNSUPPORTED, "wide profile: more rows per thread than the kernel holds");
-    DevBuf<uint64_t> d_keys, d_len, d_off, d_states;
+    ProfileKeep here;
+    ProfileKeep& kept = keep_states ? *keep_states : here;
+    DevBuf<uint64_t>&d_keys = kept.keys, &d_len = kept.lengths, &d_off = kept.offsets, &d_states = kept.states;
     DevBuf<uint32_t> d_on_here;
     DevBuf<uint32_t>& d_on = keep_on ? *keep_on : d_on_here;   // (keep_on: counted in any case, and left there)
     const bool count_on = on_counts || keep_on;
-    DevBuf<uint8_t> d_closed;
+    DevBuf<uint8_t>& d_closed = kept.closed;
+    const bool want_states = states || keep_states, want_closed = closed || keep_states;
     HIPCHK(h, d_keys.alloc(n * key_stride));
     HIPCHK(h, hipMemcpy(d_keys.p, keys, n * key_stride * 8, hipMemcpyHostToDevice));
     HIPCHK(h, d_len.alloc(n));
     HIPCHK(h, hipMemcpy(d_len.p, lengths, n * 8, hipMemcpyHostToDevice));
-    if (states) {
+    if (want_states) {
         HIPCHK(h, d_off.alloc(n));
         HIPCHK(h, hipMemcpy(d_off.p, state_offsets, n * 8, hipMemcpyHostToDevice));
         HIPCHK(h, d_states.alloc(state_words));
@@ -361,7 +375,7 @@ int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, co
         HIPCHK(h, d_on.alloc(n * W.n));
         HIPCHK(h, hipMemsetAsync(d_on.p, 0, n * W.n * sizeof(uint32_t), h->stream));
     }
-    if (closed) HIPCHK(h, d_closed.alloc(n));
+    if (want_closed) HIPCHK(h, d_closed.alloc(n));
 
     WideProfileParams Q{};
     WideParams& P = Q.net;
@@ -372,7 +386,7 @@ int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, co
     P.desc = W.d_desc.p; P.wdesc = W.wdesc.empty() ? nullptr : W.d_wdesc.p; P.wpreds = W.d_wpreds.p; P.wtt = W.d_wtt.p;
     P.n_fslots = W.n_fslots;
     Q.key_stride = key_stride;
-    Q.states = states ? d_states.p : nullptr;
+    Q.states = want_states ? d_states.p : nullptr;
     Q.ctr = W.d_ctr.p;
     const size_t shmem = (size_t)wide_profile_lds_words(W.rows, W.L, W.n_fslots) * 4;
     const uint32_t G = 32 * W.L;
@@ -385,12 +399,16 @@ int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, co
         Q.count = m;
         Q.keys = d_keys.p + at * key_stride;
         Q.lengths = d_len.p + at;
-        Q.state_offsets = states ? d_off.p + at : nullptr;
+        Q.state_offsets = want_states ? d_off.p + at : nullptr;
         Q.on_counts = count_on ? d_on.p + at * W.n : nullptr;
-        Q.closed = closed ? d_closed.p + at : nullptr;
+        Q.closed = want_closed ? d_closed.p + at : nullptr;
         const uint64_t groups = (m + G - 1) / G;
         const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>(groups, (uint64_t)h->prop.multiProcessorCount * per_cu));
         HIPCHK(h, launch_wide_profile((int)W.K, dim3((uint32_t)blocks), shmem, h->stream, Q));
+    }
+    if (keep_states) {
+        keep_states->launches = launches;
+        return BSX_OK;
     }
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     unsigned long long ctr[4] = {0, 0, 0, 0};
@@ -713,6 +731,178 @@ extern "C" int bsx_run_attract_wide(bsx_handle h, bsx_u128 first_flat, bsx_u128 
         stats->dominant_launches = launches;
         stats->kernel_launches = launches;
         stats->host_syncs = launches;
+        stats->total_ms = now_ms() - t_begin;
+    }
+    return BSX_OK;
+}
+
+// ---- attractor transitions on the wide family -----------------------------------------------------------------------
+// Host side of bsx_run_attractor_transitions_wide: argument checks, allocation, the enqueue chain
+//     profile (states and closure stay in HBM) -> k_wide_trans over the rows -> k_wide_trans_build ->
+//     k_wide_trans over the flips, BSX_WTRANS_CHUNK per launch -> k_trans_drain,
+// one wait, the flags -> status mapping and the sort of the edge list, as bsx_trans_api.cpp does for the <= 256 family.
+static_assert(kWtransOutside == kTransOutside && kWtransUnresolved == kTransUnresolved, "the pseudo-destinations");
+static_assert(kWtransInf == BSX_T_INF, "no cap");
+constexpr uint64_t kWideTransRowChunk = 1ull << 18;     // rows per launch of the rows' walks
+constexpr uint64_t kWideTransFlipChunk = 1ull << 22;    // flips per launch (BSX_WTRANS_CHUNK)
+
+extern "C" int bsx_run_attractor_transitions_wide(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths,
+                                                  uint64_t n, uint64_t max_t, bsx_trans_edge* edges, uint64_t edge_cap,
+                                                  uint64_t* n_edges, uint32_t* node_exits, uint8_t* closed, bsx_stats* stats) {
+    if (!h) return BSX_ERR_INVALID;
+    h->knobs = Knobs::from_env();
+    if (!h->have_net || !h->have_space) return fail(h, BSX_ERR_STATE, "network / problem space not set");
+    if (!h->wide) return bsx_run_attractor_transitions(h, keys, key_stride, lengths, n, max_t, edges, edge_cap, n_edges, node_exits, closed, stats);
+    const double t_begin = now_ms();
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0) return BSX_OK;
+    const std::string who = "bsx_run_attractor_transitions_wide";
+    uint64_t sum_len = 0, unused = 0;
+    if (int rc = profile_check_args(h, who.c_str(), keys, key_stride, lengths, n, nullptr, nullptr, &sum_len, &unused)) return rc;
+    if (!edges || !n_edges) return fail(h, BSX_ERR_INVALID, who + ": edges or n_edges is null");
+    if (n > 0xFFFFFFFDull) return fail(h, BSX_ERR_INVALID, who + ": more than 2^32 - 3 attractors");
+    if (sum_len > kTransMaxStates) return fail(h, BSX_ERR_UNSUPPORTED, who + ": more than 2^28 cycle states (BSX_TRANS_MAX_STATES)");
+    WideHost& W = *h->wide;
+    const size_t shmem = (size_t)wide_trans_lds_words(W.rows, W.L, W.n_fslots) * 4;
+    if (shmem > W.shmem || (size_t)W.rows * W.L * 4 < kTransLdsEdges * sizeof(TransEdgeSlot))
+        return fail(h, BSX_ERR_UNSUPPORTED, who + ": the group's tables do not fit the LDS");
+    HIPCHK(h, hipSetDevice(h->device));
+
+    const uint32_t w64 = W.w64, n_nodes = W.n;
+    std::vector<uint32_t> free_nodes;
+    for (uint32_t i = 0; i < n_nodes; ++i)
+        if (!((W.fixmask[i >> 5] >> (i & 31)) & 1u)) free_nodes.push_back(i);
+    const uint32_t n_free = (uint32_t)free_nodes.size();
+    const uint64_t flips = sum_len * n_free;                            // (< 2^28 * 2^10)
+
+    // the profile: states (row after row, the key first) and closure stay on the device; enqueued, not waited for
+    std::vector<uint64_t> offsets(n), row_first(n);
+    for (uint64_t q = 0, at = 0; q < n; at += lengths[q], ++q) { row_first[q] = at; offsets[q] = at * w64; }
+    ProfileKeep kept;
+    if (int rc = wide_run_profile(h, keys, key_stride, lengths, n, nullptr, nullptr, offsets.data(), sum_len * w64, nullptr, sum_len,
+                                  nullptr, nullptr, &kept))
+        return rc;
+
+    // row-key table: a power of two >= 2 n owners (at least 2); edge table as in bsx_trans_api.cpp
+    uint64_t n_slots = 2;
+    while (n_slots < 2 * n) n_slots <<= 1;
+    const uint64_t most_edges = n >= (1ull << 31) ? ~0ull : n * (n + 2);
+    const uint64_t out_cap = std::min({edge_cap, flips, most_edges});
+    uint64_t edge_slots = 2;
+    while (edge_slots < 2 * (out_cap + 1)) edge_slots <<= 1;           // (+ 1: one edge too many must still find a slot)
+    const uint64_t flip_chunk = h->knobs.wtrans_chunk ? std::min<uint64_t>(h->knobs.wtrans_chunk, 1ull << 28) : kWideTransFlipChunk;
+
+    // workgroups of a launch over `count` trajectories; the x_0 spill takes rows * L words per workgroup
+    const uint32_t G = 32 * W.L;
+    const uint32_t per_cu = std::max<uint32_t>(1, (uint32_t)((160 * 1024) / shmem));
+    auto blocks_for = [&](uint64_t count) {
+        return std::max<uint64_t>(1, std::min<uint64_t>((count + G - 1) / G, (uint64_t)h->prop.multiProcessorCount * per_cu));
+    };
+    const uint64_t most_blocks = std::max(blocks_for(std::min(n, kWideTransRowChunk)), blocks_for(std::min(std::max<uint64_t>(flips, 1), flip_chunk)));
+
+    DevBuf<uint64_t> d_row_first, d_row_keys;
+    DevBuf<uint32_t> d_owners, d_row_info, d_free, d_exits, d_x0;
+    DevBuf<TransEdgeSlot> d_edges;
+    DevBuf<TransEdge> d_out;
+    DevBuf<TransCtr> d_tc;
+    HIPCHK(h, d_row_first.upload(row_first));
+    HIPCHK(h, d_free.upload(free_nodes));
+    HIPCHK(h, d_row_keys.alloc(n * w64));
+    HIPCHK(h, d_row_info.alloc(2 * n));
+    HIPCHK(h, d_owners.alloc(n_slots));
+    HIPCHK(h, d_x0.alloc((size_t)most_blocks * W.rows * W.L));
+    HIPCHK(h, d_edges.alloc(edge_slots));
+    HIPCHK(h, d_out.alloc(out_cap));
+    HIPCHK(h, d_tc.alloc(1));
+    if (node_exits) HIPCHK(h, d_exits.alloc(n * n_nodes));
+    TransCtr tc{};
+    tc.open_row = tc.dup_row = kTransNoRow;
+    HIPCHK(h, hipMemcpyAsync(d_tc.p, &tc, sizeof(tc), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_owners.p, 0, n_slots * sizeof(uint32_t), h->stream));
+    HIPCHK(h, hipMemsetAsync(d_edges.p, 0, edge_slots * sizeof(TransEdgeSlot), h->stream));
+    if (node_exits) HIPCHK(h, hipMemsetAsync(d_exits.p, 0, n * n_nodes * sizeof(uint32_t), h->stream));
+
+    WideTransParams Q{};
+    WideParams& P = Q.net;
+    P.n_nodes = W.n; P.rows = W.rows; P.L = W.L;
+    P.lshift = (uint32_t)__builtin_ctz(W.L);
+    P.rows_ps = W.rows / (kWideThreads / W.L);
+    P.w64 = w64;
+    P.desc = W.d_desc.p; P.wdesc = W.wdesc.empty() ? nullptr : W.d_wdesc.p; P.wpreds = W.d_wpreds.p; P.wtt = W.d_wtt.p;
+    P.n_fslots = W.n_fslots;
+    P.max_t = max_t;
+    P.cap_inf = max_t == BSX_T_INF ? 1u : 0u;
+    P.step_limit = h->knobs.wide_step_limit;
+    P.x0 = d_x0.p;
+    Q.key_stride = key_stride;
+    Q.n_rows = n;
+    Q.keys = kept.keys.p;
+    Q.lengths = kept.lengths.p;
+    Q.closed = kept.closed.p;
+    Q.states = kept.states.p;
+    Q.row_first = d_row_first.p;
+    Q.free_nodes = d_free.p;
+    Q.n_free = n_free;
+    Q.row_info = d_row_info.p;
+    Q.row_keys = d_row_keys.p;
+    Q.owners = d_owners.p;
+    Q.slot_mask = n_slots - 1;
+    Q.edges = d_edges.p;
+    Q.edge_mask = edge_slots - 1;
+    Q.node_exits = node_exits ? d_exits.p : nullptr;
+    Q.ctr = d_tc.p;
+
+    uint32_t launches = kept.launches;
+    Q.stage = kWideTransRows;
+    for (uint64_t at = 0; at < n; at += kWideTransRowChunk, ++launches) {
+        Q.first = at;
+        Q.count = std::min<uint64_t>(kWideTransRowChunk, n - at);
+        HIPCHK(h, launch_wide_trans((int)W.K, dim3((uint32_t)blocks_for(Q.count)), shmem, h->stream, Q));
+    }
+    HIPCHK(h, launch_wide_trans_build(Q, h->stream));
+    ++launches;
+    Q.stage = kWideTransFlips;
+    for (uint64_t at = 0; at < flips; at += flip_chunk, ++launches) {
+        Q.first = at;
+        Q.count = std::min<uint64_t>(flip_chunk, flips - at);
+        HIPCHK(h, launch_wide_trans((int)W.K, dim3((uint32_t)blocks_for(Q.count)), shmem, h->stream, Q));
+    }
+    HIPCHK(h, launch_trans_drain(d_edges.p, edge_slots, d_out.p, out_cap, d_tc.p, h->stream));
+    ++launches;
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));                       // (ev0: wide_run_profile, in front of its first launch)
+    unsigned long long ctr[4] = {0, 0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(ctr, W.d_ctr.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tc, d_tc.p, sizeof(tc), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                         // the call's one wait
+
+    if (tc.open_row != kTransNoRow)
+        return fail(h, BSX_ERR_INVALID, who + ": row " + std::to_string(tc.open_row) + " is not closed: its key does not return after its length");
+    if (tc.dup_row != kTransNoRow)
+        return fail(h, BSX_ERR_INVALID, who + ": row " + std::to_string(tc.dup_row) + " lies on the cycle of another row or repeats its own "
+                                              "(a duplicate row, or a length that is a multiple of the period)");
+    if (tc.probe_full) return fail(h, BSX_ERR_HIP, who + ": the row-key table overflowed");
+    if (tc.step_limit_hits || tc.rows_undecided) return fail(h, BSX_ERR_STEP_LIMIT, who + ": a walk ran into the internal step limit");
+    if (tc.edge_overflow || tc.n_edges > edge_cap)
+        return fail(h, BSX_ERR_TABLE_FULL, who + ": more distinct edges than edge_cap");
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    std::vector<TransEdge> got(tc.n_edges);
+    if (tc.n_edges) HIPCHK(h, hipMemcpy(got.data(), d_out.p, tc.n_edges * sizeof(TransEdge), hipMemcpyDeviceToHost));
+    std::sort(got.begin(), got.end(), [](const TransEdge& a, const TransEdge& b) { return a.src != b.src ? a.src < b.src : a.dst < b.dst; });
+    uint64_t sum_mu = 0;
+    for (uint64_t e = 0; e < tc.n_edges; ++e) {
+        edges[e] = bsx_trans_edge{got[e].src, got[e].dst, got[e].count, got[e].sum_mu};
+        sum_mu += got[e].sum_mu;
+    }
+    *n_edges = tc.n_edges;
+    if (node_exits) HIPCHK(h, hipMemcpy(node_exits, d_exits.p, n * n_nodes * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (closed) HIPCHK(h, hipMemcpy(closed, kept.closed.p, n, hipMemcpyDeviceToHost));
+    if (stats) {
+        stats->problems = flips;
+        stats->state_steps = sum_mu;
+        stats->executed_steps = ctr[1] + tc.steps_exec;
+        stats->kernel_ms = ms;
+        stats->kernel_launches = launches;
         stats->total_ms = now_ms() - t_begin;
     }
     return BSX_OK;

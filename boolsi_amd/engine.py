@@ -257,6 +257,18 @@ class Engine:
         ERR_TABLE_FULL means more distinct edges than `edge_cap`, ERR_UNSUPPORTED a network on the wide-state family.
         `trans_stats` holds the call's statistics afterwards.
         """
+        return self._attractor_transitions(self._lib.bsx_run_attractor_transitions, keys, lengths, max_t, edge_cap, node_exits)
+
+    def attractor_transitions_wide(self, keys, lengths, max_t=float('inf'), edge_cap=1 << 20, node_exits=False):
+        """
+        attractor_transitions for networks of every supported size (bsx_run_attractor_transitions_wide): the same
+        arguments and the same (edges, node_exits, closed).  On the wide-state family a row may be listed from any state
+        of its cycle, and ERR_INVALID names a row that is not closed or lies on the cycle of another row; below 257 nodes
+        (without BSX_WIDE=1) the call is attractor_transitions.
+        """
+        return self._attractor_transitions(self._lib.bsx_run_attractor_transitions_wide, keys, lengths, max_t, edge_cap, node_exits)
+
+    def _attractor_transitions(self, call, keys, lengths, max_t, edge_cap, node_exits):
         W = self.net.n_words
         n = len(keys)
         ints = [int(k) for k in keys]
@@ -274,8 +286,8 @@ class Engine:
         closed = np.zeros(n, np.uint8)
         n_edges = C.c_uint64(0)
         st = Stats()
-        self._check(self._lib.bsx_run_attractor_transitions(self._h, ptr(key_words), W, ptr(lens), n, cap, edges.ctypes.data_as(C.c_void_p),
-                                                            int(edge_cap), C.byref(n_edges), ptr(exits), ptr(closed), C.byref(st)))
+        self._check(call(self._h, ptr(key_words), W, ptr(lens), n, cap, edges.ctypes.data_as(C.c_void_p), int(edge_cap),
+                         C.byref(n_edges), ptr(exits), ptr(closed), C.byref(st)))
         self.trans_stats = st.as_dict()
         return edges[:n_edges.value].copy(), exits, closed
 

@@ -359,6 +359,31 @@ int  bsx_run_attractor_transitions(bsx_handle h, const uint64_t* keys, uint32_t 
                                    uint64_t max_t, bsx_trans_edge* edges, uint64_t edge_cap, uint64_t* n_edges,
                                    uint32_t* node_exits, uint8_t* closed, bsx_stats* stats);
 
+/* bsx_run_attractor_transitions for networks of every supported size: the same arguments, semantics, outputs, refusals
+ * and statistics; keys are rows of key_stride >= W words with W up to BSX_MAX_STATE_WORDS.  On a network of the
+ * <= BSX_MAX_NODES family the call forwards to bsx_run_attractor_transitions.  On the wide-state family (more than
+ * BSX_MAX_NODES nodes, or BSX_WIDE=1) groups of flips walk in lock step, bit-sliced, and no state is looked up per
+ * step: a flip's destination cycle is identified by its canonical key (the cycle's minimum state) in a table of the
+ * rows' canonical keys, so a row may be listed from any state of its cycle.  Per flip that costs Brent's detector
+ * (at most 3 (mu + lambda') + 2 steps), the mu pass (lambda' + 2 mu) and one lap of the cycle (lambda').
+ * Refused as bsx_run_attractor_transitions refuses, before any flip is walked and with nothing written: a row that is
+ * not closed; two rows on the same cycle, or a length that is a proper multiple of the true period (BSX_ERR_INVALID, the
+ * text names the later row).  n == 0 is BSX_OK.  The step limit of this family counts lock steps of a group (2^24, or
+ * BSX_WIDE_STEP_LIMIT); a max_t at or beyond a quarter of it is walked as unbounded (the result is still exact), and a
+ * walk that reaches the limit undecided -- a flip's, or a row's own -- makes the call return BSX_ERR_STEP_LIMIT.
+ * One host wait; the handle's problem space, cycle journal and mirror image are left alone.  stats as above, with
+ * executed_steps = the trajectory updates of the profile, the rows' walks and the flips' walks.  One launch of the flips'
+ * kernel per 2^22 flips (BSX_WTRANS_CHUNK changes that).
+ * Device memory, from the allocation sizes: per cycle state 8 W bytes of state; per row 8 W bytes of canonical key,
+ * 8 * key_stride of key, 8 bytes of period and mu, 8 to 16 bytes of row-key table (4 bytes a slot, a power of two >=
+ * 2 n), 25 bytes of lengths, offsets, first-state index and closure, 4 * n_nodes with node_exits; 24 bytes per
+ * edge-table slot (a power of two >= 2 * min(edge_cap, flips, n (n + 2)) + 2) and 24 per edge record; 4 * rows * L bytes
+ * of spilled start states per workgroup (rows = n_nodes rounded up to 64, L <= 64 columns, a few workgroups per compute
+ * unit).  At BSX_TRANS_MAX_STATES states of 1024 nodes the states alone are 32 GiB. */
+int  bsx_run_attractor_transitions_wide(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths,
+                                        uint64_t n, uint64_t max_t, bsx_trans_edge* edges, uint64_t edge_cap, uint64_t* n_edges,
+                                        uint32_t* node_exits, uint8_t* closed, bsx_stats* stats);
+
 /* Blocks until all work of the handle's stream is done (bench.py's timing fence). */
 int  bsx_synchronize(bsx_handle h);
 

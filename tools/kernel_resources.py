@@ -48,6 +48,8 @@ LAUNCHED = {
     'bsx::k_trans_drain': 'attractor transitions: edge table to records, once per call',
     'bsx::k_trans_walk<1, 2, 1>': 'attractor transitions: tools/bench_transitions.py, table "mixed" (n = 16)',
     'bsx::k_trans_walk<2, 2, 1>': 'attractor transitions: tools/bench_transitions.py, table "north_star" (n = 64, K = 2)',
+    'bsx::k_wide_trans<2, false>': 'attractor transitions of wide networks: rows and flips, tools/bench_transitions_wide.py',
+    'bsx::k_wide_trans_build': 'attractor transitions of wide networks: row-key table in HBM, once per call',
 }
 
 
