@@ -107,10 +107,14 @@ __global__ __launch_bounds__(kBlock, NW <= 2 ? 4 : 2) void k_target(const Target
             uint32_t nxt[NW];
             net_step<NW, K>(nv, A, fm, fv, nxt);
             if (phase == PH_BRENT) {
-                const bool reached = target_hit<NW>(A, tm, tc) && !(skip0 && t == 0);
+                // cube pass, t = 0: A is the representative's s(0), not the other members', so it is neither a hit of theirs
+                // nor a state of theirs that has been checked -- a representative that is a fixed point closes no cycle
+                // here: the members reach it at t = 1 and it is checked then
+                const bool rep0 = skip0 && t == 0;
+                const bool reached = target_hit<NW>(A, tm, tc) && !rep0;
                 const bool capped = !reached && t >= t_cap;
                 const uint32_t lam1 = lam + 1;
-                const bool closed = !reached && !capped && eq_words<NW>(nxt, B);     // every state has been checked
+                const bool closed = !reached && !capped && !rep0 && eq_words<NW>(nxt, B);     // every state has been checked
                 const bool tele = !closed && lam1 == power;
                 if (reached | capped | closed) {
                     if (P.t_hit) P.t_hit[my_p] = reached ? t : kNotReached;
