@@ -16,6 +16,7 @@
 #include "bsx_cube_plan.h"
 #include "bsx_engine.h"
 #include "bsx_host.h"
+#include "bsx_wide_lower.h"
 
 using namespace bsx;
 
@@ -155,7 +156,7 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     if (n_nodes == 0 || !pred_offsets || !tt_word_offsets || !tt_words)
         return fail(h, BSX_ERR_INVALID, "bsx_set_network: null table or zero nodes");
     h->knobs = Knobs::from_env();
-    if (n_nodes > BSX_MAX_NODES || h->knobs.wide)          // the wide-state family (bsx_wide_api.cpp)
+    if (n_nodes > BSX_MAX_NODES || h->knobs.wide)          // the wide-state family (bsx_wide_host.h)
         return wide_set_network(h, n_nodes, pred_offsets, pred_idx, tt_word_offsets, tt_words);
     wide_release(h);
     HIPCHK(h, hipSetDevice(h->device));
@@ -165,19 +166,9 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     const uint32_t nw = n_nodes <= 32 ? 1 : n_nodes <= 64 ? 2 : n_nodes <= 128 ? 4 : 8;
     uint32_t k_mux = 1;
     std::vector<uint32_t> wide;
+    if (const LowerStatus s = check_network_arrays(n_nodes, pred_offsets, pred_idx, tt_word_offsets)) return fail(h, s.status, s.msg);
     for (uint32_t i = 0; i < n_nodes; ++i) {
-        if (pred_offsets[i + 1] < pred_offsets[i]) return fail(h, BSX_ERR_INVALID, "pred_offsets not monotone");
         const uint32_t k = pred_offsets[i + 1] - pred_offsets[i];
-        if (k > BSX_MAX_PREDECESSORS) return fail(h, BSX_ERR_UNSUPPORTED, "node with more than BSX_MAX_PREDECESSORS predecessors");
-        if (k && !pred_idx) return fail(h, BSX_ERR_INVALID, "pred_idx is null");
-        for (uint32_t j = pred_offsets[i]; j < pred_offsets[i + 1]; ++j) {
-            if (pred_idx[j] >= n_nodes) return fail(h, BSX_ERR_INVALID, "predecessor index out of range");
-            if (j > pred_offsets[i] && pred_idx[j] <= pred_idx[j - 1])
-                return fail(h, BSX_ERR_INVALID, "predecessors must be strictly ascending");
-        }
-        const uint32_t need_words = k <= 6 ? 1u : (1u << (k - 6));
-        if (tt_word_offsets[i + 1] - tt_word_offsets[i] != need_words)
-            return fail(h, BSX_ERR_INVALID, "truth table of a node must have ceil(2^k / 64) words");
         if (k > (uint32_t)kMaxMuxK) wide.push_back(i);
         else k_mux = std::max(k_mux, k);
     }
@@ -441,21 +432,8 @@ static int launch_target_pass(bsx_handle h, const bsx_index* first, uint64_t ski
     TargetParams P{};
     P.net = h->net;
     P.sp = h->sp;
-    set_first(P.sp, first);
-    if (skip) {                                 // first + skip, carrying into the variant (init_problem adds the offset the same way)
-        unsigned __int128 carry = skip;
-        for (int w = 0; w < 4; ++w) { carry += P.sp.first_digits[w]; P.sp.first_digits[w] = (uint64_t)carry; carry >>= 64; }
-        const uint32_t n_any = h->sp.n_any;
-        if (n_any < 256) {
-            // digits at or above n_any belong to the variant number
-            uint64_t over = 0;
-            for (uint32_t b = n_any; b < 256 && b < n_any + 64; ++b) {
-                over |= ((P.sp.first_digits[b >> 6] >> (b & 63)) & 1ull) << (b - n_any);
-                P.sp.first_digits[b >> 6] &= ~(1ull << (b & 63));
-            }
-            P.sp.first_variant += over;
-        }
-    }
+    const bsx_index at = index_plus(*first, skip, h->sp.n_any);     // (init_problem adds the offset the same way)
+    set_first(P.sp, &at);
     P.count = count;
     P.chunk = L.chunk;
     P.cap_rel_inf = max_t == BSX_T_INF ? 1 : 0;
@@ -523,30 +501,7 @@ extern "C" int bsx_run_target(bsx_handle h, const bsx_index* first, uint64_t cou
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (count == 0) return BSX_OK;
     if (count > (1ull << 32)) return fail(h, BSX_ERR_INVALID, "at most 2^32 problems per call");
-    if (h->wide) {
-        // per-problem first-hit times of the wide kernel, listed here (chunks of 2^24 problems)
-        uint64_t total = 0;
-        bsx_stats part{};
-        if (stats) stats->problems = count;
-        for (uint64_t done = 0; done < count; done += 1ull << 24) {
-            const uint64_t m = std::min<uint64_t>(1ull << 24, count - done);
-            const bsx_index at = index_plus(*first, done, h->sp.n_any);
-            std::vector<uint32_t> t_hit;
-            if (int rc = wide_target_times(h, &at, m, max_t, mask_words, code_words, t_hit, &part)) return rc;
-            for (uint64_t p = 0; p < m; ++p) {
-                if (t_hit[p] == 0xFFFFFFFFu) continue;
-                if (total == cap) return fail(h, BSX_ERR_TABLE_FULL, "more hits than the caller's capacity (bsx_run_target_summary counts without listing)");
-                hits[total++] = bsx_hit{done + p, t_hit[p]};
-            }
-            if (stats) {
-                stats->state_steps += part.state_steps; stats->executed_steps += part.executed_steps;
-                stats->kernel_ms += part.kernel_ms; stats->kernel_launches += part.kernel_launches;
-            }
-        }
-        *n_hits = total;
-        if (stats) stats->total_ms = now_ms() - t_begin;
-        return BSX_OK;
-    }
+    if (h->wide) return wide_run_target(h, first, count, max_t, mask_words, code_words, hits, cap, n_hits, stats, t_begin);
     DevBuf<uint32_t> d_thit;
     HIPCHK(h, d_thit.alloc(count));
     Counters ctr{};
@@ -556,14 +511,7 @@ extern "C" int bsx_run_target(bsx_handle h, const bsx_index* first, uint64_t cou
     if (total_hits > cap) return fail(h, BSX_ERR_TABLE_FULL, "more hits than the caller's capacity (bsx_run_target_summary counts without listing)");
     if (int rc = compact_hits(h, d_thit.p, count, total_hits, 0, hits, cap)) return rc;
     *n_hits = total_hits;
-    if (stats) {
-        stats->problems = count;
-        stats->state_steps = ctr.steps_ref;
-        stats->executed_steps = ctr.steps_exec;
-        stats->kernel_ms = ms;
-        stats->kernel_launches = 1;
-        stats->total_ms = now_ms() - t_begin;
-    }
+    put_stats(stats, count, ctr.steps_ref, ctr.steps_exec, ms, 1, t_begin);
     if (ctr.step_limit_hits) return fail(h, BSX_ERR_STEP_LIMIT, "a trajectory reached the internal step limit");
     return BSX_OK;
 }
@@ -588,34 +536,7 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (count == 0) return BSX_OK;
     if (count > (1ull << 40)) return fail(h, BSX_ERR_INVALID, "at most 2^40 problems per call");
-    if (h->wide && !h->knobs.wide_host_reduce)         // counted and binned on the device (bsx_wide_reduce.hip)
-        return wide_target_summary(h, first, count, max_t, mask_words, code_words, hist, hist_bins, hits, cap, n_hits, n_listed, stats);
-    if (h->wide) {
-        // BSX_WIDE_HOST_REDUCE=1: per-problem first-hit times of the wide kernel, summarised here (chunks of 2^24 problems)
-        uint64_t total = 0, listed = 0;
-        bsx_stats part{};
-        if (stats) stats->problems = count;
-        for (uint64_t done = 0; done < count; done += 1ull << 24) {
-            const uint64_t m = std::min<uint64_t>(1ull << 24, count - done);
-            const bsx_index at = index_plus(*first, done, h->sp.n_any);
-            std::vector<uint32_t> t_hit;
-            if (int rc = wide_target_times(h, &at, m, max_t, mask_words, code_words, t_hit, &part)) return rc;
-            for (uint64_t p = 0; p < m; ++p) {
-                if (t_hit[p] == 0xFFFFFFFFu) continue;
-                ++total;
-                if (hist_bins) ++hist[std::min<uint64_t>(t_hit[p], hist_bins - 1)];
-                if (listed < cap) hits[listed++] = bsx_hit{done + p, t_hit[p]};
-            }
-            if (stats) {
-                stats->state_steps += part.state_steps; stats->executed_steps += part.executed_steps;
-                stats->kernel_ms += part.kernel_ms; stats->kernel_launches += part.kernel_launches;
-            }
-        }
-        *n_hits = total;
-        if (n_listed) *n_listed = listed;
-        if (stats) stats->total_ms = now_ms() - t_begin;
-        return BSX_OK;
-    }
+    if (h->wide) return wide_run_target_summary(h, first, count, max_t, mask_words, code_words, hist, hist_bins, hits, cap, n_hits, n_listed, stats, t_begin);
 
     DevBuf<unsigned long long> d_hist;              // (one bin even if the caller wants none: the kernels count into it)
     HIPCHK(h, d_hist.alloc(std::max<uint32_t>(hist_bins, 1)));
@@ -779,14 +700,7 @@ extern "C" int bsx_run_target_summary(bsx_handle h, const bsx_index* first, uint
     if (hist_bins) HIPCHK(h, hipMemcpy(hist, d_hist.p, hist_bins * sizeof(uint64_t), hipMemcpyDeviceToHost));
     *n_hits = total;
     if (n_listed) *n_listed = listed;
-    if (stats) {
-        stats->problems = count;
-        stats->state_steps = steps_ref;
-        stats->executed_steps = steps_exec;
-        stats->kernel_ms = kernel_ms;
-        stats->kernel_launches = launches;
-        stats->total_ms = now_ms() - t_begin;
-    }
+    put_stats(stats, count, steps_ref, steps_exec, kernel_ms, launches, t_begin);
     if (limit_hits) return fail(h, BSX_ERR_STEP_LIMIT, "a trajectory reached the internal step limit");
     return BSX_OK;
 }
@@ -838,14 +752,7 @@ static int run_sim_common(bsx_handle h, const bsx_index* first, uint64_t count, 
     if (trajectories) HIPCHK(h, hipMemcpy(trajectories, d_traj.p, traj_words * 8, hipMemcpyDeviceToHost));
     if (final_states) HIPCHK(h, hipMemcpy(final_states, d_final.p, count * W * 8, hipMemcpyDeviceToHost));
     if (digests) HIPCHK(h, hipMemcpy(digests, d_dig.p, count * 8, hipMemcpyDeviceToHost));
-    if (stats) {
-        stats->problems = count;
-        stats->state_steps = ctr.steps_ref;
-        stats->executed_steps = ctr.steps_exec;
-        stats->kernel_ms = ms;
-        stats->kernel_launches = 1;
-        stats->total_ms = now_ms() - t_begin;
-    }
+    put_stats(stats, count, ctr.steps_ref, ctr.steps_exec, ms, 1, t_begin);
     return BSX_OK;
 }
 
@@ -910,14 +817,7 @@ static int run_sim_sliced(bsx_handle h, const bsx_index* first, uint64_t count, 
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
     if (final_states) HIPCHK(h, hipMemcpy(final_states, d_final.p, count * W * 8, hipMemcpyDeviceToHost));
     if (digests) HIPCHK(h, hipMemcpy(digests, d_dig.p, count * 8, hipMemcpyDeviceToHost));
-    if (stats) {
-        stats->problems = count;
-        stats->state_steps = ctr.steps_ref;
-        stats->executed_steps = ctr.steps_exec;
-        stats->kernel_ms = ms;
-        stats->kernel_launches = 1;
-        stats->total_ms = now_ms() - t_begin;
-    }
+    put_stats(stats, count, ctr.steps_ref, ctr.steps_exec, ms, 1, t_begin);
     return BSX_OK;
 }
 

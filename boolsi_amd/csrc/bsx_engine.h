@@ -1,6 +1,6 @@
 // Host-side internals shared by the translation units behind include/bsx.h (bsx_api.cpp, bsx_attract_api.cpp,
-// bsx_cascade.cpp, bsx_fgraph_api.cpp, bsx_wide_api.cpp, bsx_comm.cpp): the engine handle, device buffers, error
-// plumbing.  Not part of the ABI.
+// bsx_cascade.cpp, bsx_fgraph_api.cpp, bsx_wide_api.cpp, bsx_wide_attract_api.cpp, bsx_wide_trans_api.cpp,
+// bsx_comm.cpp): the engine handle, device buffers, error plumbing.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,7 +16,7 @@
 
 namespace bsx {
 
-struct WideHost;        // bsx_wide_api.cpp
+struct WideHost;        // bsx_wide_host.h
 
 template <typename T>
 struct DevBuf {
@@ -143,7 +143,7 @@ struct bsx_engine {
     bsx::DevBuf<uint32_t> d_fg_a, d_fg_b, d_fg_c, d_fg_warm;
     bsx::DevBuf<unsigned long long> d_fg_pair;
 
-    // wide-state family (bsx_wide_api.cpp): set when the network has more than BSX_MAX_NODES nodes or BSX_WIDE=1
+    // wide-state family (bsx_wide_host.h, bsx_wide_*api.cpp): set when the network has more than BSX_MAX_NODES nodes or BSX_WIDE=1
     bsx::WideHost* wide = nullptr;
 
     // RCCL communicator of this handle's rank (bsx_comm.cpp); librccl is loaded on first use
@@ -172,11 +172,11 @@ int wide_run_simulate(bsx_handle h, const bsx_index* first, uint64_t count, uint
                       uint64_t* final_states, uint64_t* digests, bsx_stats* stats);
 int wide_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* offsets, const uint64_t* t_len, uint64_t n,
                           uint64_t* out, const uint64_t* out_offsets, bsx_stats* stats);
-int wide_target_times(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
-                      const uint64_t* code_words, std::vector<uint32_t>& t_hit, bsx_stats* stats);
-int wide_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
-                        const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
-                        uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats);
+int wide_run_target(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
+                    const uint64_t* code_words, bsx_hit* hits, uint64_t cap, uint64_t* n_hits, bsx_stats* stats, double t_begin);
+int wide_run_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
+                            const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
+                            uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats, double t_call);
 int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
                      uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
                      uint64_t sum_len, bsx_stats* stats, DevBuf<uint32_t>* keep_on, ProfileKeep* keep_states = nullptr);

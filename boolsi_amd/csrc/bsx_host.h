@@ -1,5 +1,5 @@
 // Host-side helpers shared by the translation units behind include/bsx.h (bsx_api.cpp: handle, network, problem
-// space, target, simulate; bsx_attract_host.h: attract; bsx_wide_api.cpp): kernel launch prototypes, range checks,
+// space, target, simulate; bsx_attract_host.h: attract; bsx_wide_host.h: the wide family): kernel launch prototypes, range checks,
 // index arithmetic.  Not part of the ABI.  (Wide integers and the merge: bsx_merge.h; the cube analysis: bsx_cube_plan.h.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -144,6 +144,18 @@ inline bsx_index index_plus(const bsx_index& first, u128 delta, uint32_t n_any) 
 inline double now_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// The statistics of a finished call that began at t_begin (now_ms)
+inline void put_stats(bsx_stats* stats, uint64_t problems, uint64_t state_steps, uint64_t executed_steps, double kernel_ms,
+                      uint32_t launches, double t_begin) {
+    if (!stats) return;
+    stats->problems = problems;
+    stats->state_steps = state_steps;
+    stats->executed_steps = executed_steps;
+    stats->kernel_ms = kernel_ms;
+    stats->kernel_launches = launches;
+    stats->total_ms = now_ms() - t_begin;
 }
 
 }  // namespace bsx

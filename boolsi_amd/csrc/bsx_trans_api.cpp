@@ -5,7 +5,7 @@
 // (a row that does not close, two rows that share a state) is left in TransCtr by k_trans_build; k_trans_walk looks
 // at it first and walks nothing, so such a table is refused with nothing written although the host waits only once.
 // The handle's problem space, cycle journal and mirror image are not touched.
-// Networks on the wide-state family are refused here; bsx_run_attractor_transitions_wide (bsx_wide_api.cpp) serves them.
+// Networks on the wide-state family are refused here; bsx_run_attractor_transitions_wide (bsx_wide_trans_api.cpp) serves them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

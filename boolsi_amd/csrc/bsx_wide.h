@@ -1,5 +1,5 @@
 // Wide-state family (257 <= n <= BSX_MAX_NODES_WIDE, or any n with BSX_WIDE=1): kernel parameters shared by
-// bsx_wide.hip and bsx_wide_api.cpp.  See DESIGN.md "Wide networks".
+// bsx_wide.hip, bsx_wide_lower.cpp and the host files behind bsx_wide_host.h.  See DESIGN.md "Wide networks".
 //
 // Bit-sliced like k_simulate_sliced: a group of 32 * L trajectories is a rows x L matrix of 32-bit words in LDS,
 // row i = node i, column c = trajectories 32c .. 32c + 31, bit b of a word = trajectory 32c + b.  The 256 threads
@@ -121,7 +121,7 @@ struct WideTransParams {
     TransCtr* ctr;
 };
 // LDS words of k_wide_trans: k_wide's layout without perturbation variations (never more than wide_lds_words gives
-// for the L that wide_set_problem_space chose); the group's edge table lies in the first matrix, dead by then.
+// for the L that wide_lower_space chose); the group's edge table lies in the first matrix, dead by then.
 inline uint32_t wide_trans_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslots) {
     return kWideBuffers * rows * L + 2 * n_fslots * L + 2 * kWideThreads + 8 * L + 4 * 32 * L + 8;
 }

@@ -1,0 +1,73 @@
+// Private to the host files of the wide-state family (bsx_wide_api.cpp: network, space, simulate, target, profile;
+// bsx_wide_attract_api.cpp: bsx_run_attract_wide; bsx_wide_trans_api.cpp: bsx_run_attractor_transitions_wide): the
+// family's part of a handle, the kernel launch prototypes and the one launch setup all three share.
+#pragma once
+#include "bsx_engine.h"
+#include "bsx_host.h"
+#include "bsx_wide.h"
+#include "bsx_wide_lower.h"
+
+namespace bsx {
+
+hipError_t launch_wide(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& P);
+hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, const WideProfileParams& Q);
+hipError_t launch_wide_trans(int k, dim3 grid, size_t shmem, hipStream_t st, const WideTransParams& Q);
+hipError_t launch_wide_trans_build(const WideTransParams& Q, hipStream_t st);
+hipError_t launch_wide_reduce_attract(const uint32_t* info, const uint64_t* keys, uint64_t m, uint32_t w64, WideSlot* table,
+                                      uint64_t slots, unsigned long long* hdr, hipStream_t st);
+hipError_t launch_wide_reduce_drain(const WideSlot* table, uint64_t slots, WideAttrRec* out, uint64_t cap, unsigned long long* hdr,
+                                    const unsigned long long* ctr, hipStream_t st);
+hipError_t launch_wide_reduce_target(const uint32_t* t_hit, uint64_t m, unsigned long long* hist, uint32_t bins,
+                                     unsigned long long* hdr, hipStream_t st);
+
+struct WideHost {
+    WideNet net;                // what bsx_wide_lower.cpp made of the network ...
+    WideSpace space;            // ... and of the problem space (valid while have_space)
+    bool have_space = false;
+    DevBuf<uint32_t> d_desc, d_wdesc, d_wpreds, d_wtt, d_any, d_fv, d_pv, d_sched, d_x0;
+    DevBuf<unsigned long long> d_ctr;
+    // device-side reduction (bsx_wide_reduce.hip): grow-only, reused from call to call
+    DevBuf<uint32_t> d_info, d_thit;
+    DevBuf<uint64_t> d_keys;
+    DevBuf<WideSlot> d_table;
+    DevBuf<unsigned long long> d_out, d_hist;   // d_out: kHdrWords header words, then the drained records
+};
+
+// The network part of a WideParams: layout, row descriptors, the tables of the nodes with more than 6 predecessors.
+inline void wide_fill_net(const WideHost& W, WideParams& P) {
+    const uint32_t rows = W.net.rows, L = W.space.L;
+    P.n_nodes = W.net.n; P.rows = rows; P.L = L;
+    P.lshift = (uint32_t)__builtin_ctz(L); P.w64 = W.net.w64;
+    P.rows_ps = rows / (kWideThreads / L);
+    P.desc = W.d_desc.p; P.wdesc = W.net.wdesc.empty() ? nullptr : W.d_wdesc.p; P.wpreds = W.d_wpreds.p; P.wtt = W.d_wtt.p;
+    P.n_fslots = W.space.n_fslots;
+}
+
+// Workgroups of a launch over `count` trajectories with `shmem` bytes of LDS each.
+inline uint64_t wide_blocks(const bsx_engine* h, uint64_t count, size_t shmem) {
+    return wide_grid_blocks(count, h->wide->space.L, shmem, (uint32_t)h->prop.multiProcessorCount);
+}
+
+// The end of a timed run of launches (the caller has zeroed d_ctr and recorded ev0 in front of it): records ev1, brings the
+// four counters back (and `bytes` of a caller's own counter block with them), waits, reads the device time.
+inline int wide_timed_wait(bsx_handle h, unsigned long long (&ctr)[4], float& ms, void* also = nullptr, const void* d_also = nullptr, size_t bytes = 0) {
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ctr, h->wide->d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, h->stream));
+    if (bytes) HIPCHK(h, hipMemcpyAsync(also, d_also, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    return BSX_OK;
+}
+
+// Problems per k_wide launch of a chunked run: BSX_WIDE_CHUNK clamped to [32 * L, 2^18], else `dflt`.
+inline uint64_t wide_chunk(const bsx_engine* h, uint64_t dflt) {
+    if (!h->knobs.wide_chunk_set) return dflt;
+    return std::max<uint64_t>(32ull * h->wide->space.L, std::min<uint64_t>(h->knobs.wide_chunk, 1ull << 18));
+}
+
+// bsx_wide_api.cpp: one k_wide launch enqueued; one launch waited for
+int wide_enqueue(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t);
+int wide_launch(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t, unsigned long long (&ctr)[4],
+                float& ms);
+
+}  // namespace bsx

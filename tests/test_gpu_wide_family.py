@@ -209,6 +209,30 @@ def test_composed_512_node_network(eng):
     assert e.value.status == _lib.ERR_UNSUPPORTED
 
 
+# ---- bsx_run_target's capacity check on a wide engine ----------------------------------------------
+
+def test_wide_target_list_at_and_below_its_capacity(eng):
+    """The 300-node copy ring of test_gpu_wide_reduce.py, 2^10 problems: with cap = hits the list is the exact
+    reference's, with one less the call returns BSX_ERR_TABLE_FULL and the engine goes on working."""
+    from test_gpu_wide_reduce import RING_YAML
+    from wide_ref import WideRef
+    net, space = compile_problem(parse_input_text(RING_YAML, math.inf, Mode.ATTRACT))
+    eng.set_problem(net, space)
+    assert eng.wide
+    first, count, max_t, nodes = 0, 1 << 10, 150, (100, 103)
+    code = sum(1 << i for i in nodes)
+    ref = [(q, t) for q, (reached, t) in enumerate(WideRef(net, space).target(range(first, first + count), max_t, nodes, code))
+           if reached]
+    assert 1 < len(ref) < count
+    words = code_to_words(code, net.n_words)
+    listed = lambda hits: [(int(h['offset']), int(h['t'])) for h in hits]
+    assert listed(eng.target(first, count, max_t, words, words, cap=len(ref))[0]) == ref
+    with pytest.raises(_lib.EngineError) as e:
+        eng.target(first, count, max_t, words, words, cap=len(ref) - 1)
+    assert e.value.status == _lib.ERR_TABLE_FULL
+    assert listed(eng.target(first, count, max_t, words, words)[0]) == ref
+
+
 # ---- CLI at n = 300 --------------------------------------------------------------------------------
 
 def test_cli_on_a_300_node_network(tmp_path):
