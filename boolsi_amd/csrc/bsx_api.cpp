@@ -717,6 +717,9 @@ static int run_sim_common(bsx_handle h, const bsx_index* first, uint64_t count, 
     const uint32_t W = h->w64;
     DevBuf<uint64_t> d_traj, d_final, d_dig, d_off, d_tlen, d_ooff;
     if (trajectories) HIPCHK(h, d_traj.alloc(traj_words));
+    // scattered trajectories: the whole buffer comes back in one copy, so the words between them make the round trip
+    // (a caller's buffer keeps what no trajectory covers)
+    if (trajectories && out_offsets) HIPCHK(h, hipMemcpy(d_traj.p, trajectories, traj_words * 8, hipMemcpyHostToDevice));
     if (final_states) HIPCHK(h, d_final.alloc(count * W));
     if (digests) HIPCHK(h, d_dig.alloc(count));
     if (offsets) { HIPCHK(h, d_off.alloc(count)); HIPCHK(h, hipMemcpy(d_off.p, offsets, count * 8, hipMemcpyHostToDevice)); }
@@ -740,6 +743,7 @@ static int run_sim_common(bsx_handle h, const bsx_index* first, uint64_t count, 
 
     const uint32_t cus = (uint32_t)h->prop.multiProcessorCount;
     const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cus * 4, (count + kBlock - 1) / kBlock));
+    if (h->knobs.debug && !offsets) std::fprintf(stderr, "[bsx] simulate: per-lane, %llu blocks\n", (unsigned long long)blocks);
     HIPCHK(h, hipMemsetAsync(h->d_ctr, 0, sizeof(Counters), h->stream));
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     HIPCHK(h, launch_simulate((int)h->net.nw, (int)h->net.k_mux, h->lut_mode, dim3((uint32_t)blocks), h->shmem, h->stream, P));
@@ -801,10 +805,13 @@ static int run_sim_sliced(bsx_handle h, const bsx_index* first, uint64_t count, 
 
     // K <= 3 and n <= 128: second-generation kernel (8-byte rows, constants in registers); BSX_SLICED=1 keeps the first
     const bool gen2 = K <= 3 && rows <= 128 && h->knobs.sliced != 1;
-    const size_t shmem = gen2 ? (size_t)rows * 1024 + (4096 + 64) * 4 : (size_t)rows * (8 + 128) * 4;
+    // (first generation: descriptors, buffer 0, buffer 1; buffer 1, the last, is also the scratch of the initial
+    // transposition, 32 x 64 words, which 16 rows do not hold)
+    const size_t shmem = gen2 ? (size_t)rows * 1024 + (4096 + 64) * 4 : ((size_t)rows * (8 + 64) + (size_t)std::max(rows, 32u) * 64) * 4;
     const uint64_t groups = gen2 ? (count + 4095) / 4096 : (count + 2047) / 2048;
     const uint64_t per_cu = gen2 ? 1 : std::max<size_t>(1, (160 * 1024) / shmem);
     const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>(groups, (uint64_t)h->prop.multiProcessorCount * per_cu));
+    if (h->knobs.debug) std::fprintf(stderr, "[bsx] simulate: %s, %llu blocks, %llu groups\n", gen2 ? "sliced64" : "sliced", (unsigned long long)blocks, (unsigned long long)groups);
     HIPCHK(h, hipMemsetAsync(h->d_ctr, 0, sizeof(Counters), h->stream));
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     if (gen2) HIPCHK(h, launch_simulate_sliced64((int)h->net.nw, (int)K, dim3((uint32_t)blocks), shmem, h->stream, P));

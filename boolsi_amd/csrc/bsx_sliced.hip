@@ -23,7 +23,7 @@ __global__ __launch_bounds__(64 * kSlicedWaves) void k_simulate_sliced(const Sli
     const uint32_t rows_per_wave = rows / kSlicedWaves;
     uint32_t* desc = smem;                      // [rows][8]
     uint32_t* buf0 = desc + rows * 8;           // [rows][64]
-    uint32_t* buf1 = buf0 + rows * 64;
+    uint32_t* buf1 = buf0 + rows * 64;          // [max(rows, 32)][64]: also the 32 x 64 scratch of the transposition below
     for (uint32_t i = threadIdx.x; i < rows * 8; i += blockDim.x) desc[i] = P.desc[i];
 
     const uint64_t n_groups = (P.count + 2047) / 2048;
