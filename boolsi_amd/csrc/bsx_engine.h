@@ -1,5 +1,5 @@
-// Host-side internals shared by the translation units behind include/bsx.h (bsx_api.cpp, bsx_attract_api.cpp,
-// bsx_cascade.cpp, bsx_fgraph_api.cpp, bsx_wide_api.cpp, bsx_wide_attract_api.cpp, bsx_wide_trans_api.cpp,
+// Host-side internals shared by the translation units behind include/bsx.h (bsx_api.cpp, bsx_target_api.cpp,
+// bsx_simulate_api.cpp, bsx_attract_api.cpp, bsx_cascade.cpp, bsx_fgraph_api.cpp, bsx_wide_api.cpp, bsx_wide_attract_api.cpp, bsx_wide_trans_api.cpp,
 // bsx_comm.cpp): the engine handle, device buffers, error plumbing.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -108,7 +108,7 @@ struct bsx_engine {
     bsx::DevBuf<uint32_t> d_life;       // cube collapse: per-digit influence lifetimes (ordering heuristic)
     bsx::DevBuf<uint32_t> d_lut, d_masks, d_wide_desc, d_wide_preds, d_wide_tt;
 
-    // host copies of the network and the space: the cube planner's input, the sliced simulate kernel's node descriptors
+    // host copies of the network and the space (filled by bsx_lane_lower.cpp): the cube planner's input, the sliced simulate kernel's node descriptors
     bsx::HostModel model;
 
     // problem space

@@ -1,6 +1,7 @@
 // Host-side helpers shared by the translation units behind include/bsx.h (bsx_api.cpp: handle, network, problem
-// space, target, simulate; bsx_attract_host.h: attract; bsx_wide_host.h: the wide family): kernel launch prototypes, range checks,
-// index arithmetic.  Not part of the ABI.  (Wide integers and the merge: bsx_merge.h; the cube analysis: bsx_cube_plan.h.)
+// space; bsx_lane_host.h: target, simulate; bsx_attract_host.h: attract; bsx_wide_host.h: the wide family): kernel launch
+// prototypes, range checks.  Not part of the ABI.  (Wide integers and the merge: bsx_merge.h; the cube analysis:
+// bsx_cube_plan.h; the index arithmetic: bsx_lane_lower.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "bsx_engine.h"
+#include "bsx_lane_lower.h"
 #include "bsx_merge.h"
 
 namespace bsx {
@@ -73,38 +75,10 @@ inline Launch plan_persistent(const bsx_engine* h, uint64_t count, size_t shmem)
     return Launch{dim3((uint32_t)blocks), (uint32_t)chunk};
 }
 
-// [first, first + count) must lie inside the problem space (2^n_any initial states x variants): the fast
-// enumeration paths add the offset to the digits without looking, so an over-long range would otherwise
-// spill into nodes that are not 'any' and return plausible but wrong counts.
+// bsx_lane_lower.h's range_check against the handle's problem space
 inline int check_range(bsx_handle h, const bsx_index* first, u128 count) {
-    if (!first) return fail(h, BSX_ERR_INVALID, "first index is null");
-    const uint32_t n_any = h->sp.n_any;
-    for (uint32_t b = n_any; b < 64 * BSX_MAX_WORDS; ++b)
-        if ((first->init_digits[b >> 6] >> (b & 63)) & 1ull)
-            return fail(h, BSX_ERR_INVALID, "init_digits has bits at or above n_any");
-    if (!h->variant_count_saturated && first->variant >= h->variant_count)
-        return fail(h, BSX_ERR_INVALID, "variant number outside the problem space");
-    if (count == 0) return BSX_OK;
-    // last = init_digits + (count - 1), up to 257 bits; what lies above bit n_any carries into the variant
-    uint64_t sum[6] = {0, 0, 0, 0, 0, 0};
-    u128 add = count - 1, carry = 0;
-    for (int w = 0; w < 5; ++w) {
-        carry += (w < 4 ? first->init_digits[w] : 0ull);
-        carry += (uint64_t)add;
-        add >>= 64;
-        sum[w] = (uint64_t)carry;
-        carry >>= 64;
-    }
-    sum[5] = (uint64_t)carry;
-    u128 over = 0;                                          // (sum >> n_any); at most 129 bits, of which 128 are kept ...
-    for (uint32_t b = n_any; b < 384 && b < n_any + 128; ++b)
-        over |= (u128)((sum[b >> 6] >> (b & 63)) & 1ull) << (b - n_any);
-    bool beyond = false;                                    // ... and anything above them is past every space
-    for (uint32_t b = n_any + 128; b < 384; ++b) beyond = beyond || ((sum[b >> 6] >> (b & 63)) & 1ull);
-    const u128 last_variant = (u128)first->variant + over;
-    if (beyond || (last_variant >> 64) != 0 || (!h->variant_count_saturated && (uint64_t)last_variant >= h->variant_count))
-        return fail(h, BSX_ERR_INVALID, "first + count runs past the end of the problem space");
-    return BSX_OK;
+    const LowerStatus s = range_check(first, count, h->sp.n_any, h->variant_count, h->variant_count_saturated);
+    return s ? fail(h, s.status, s.msg) : BSX_OK;
 }
 
 inline int check_max_t(bsx_handle h, uint64_t max_t) {
@@ -116,29 +90,6 @@ inline int check_max_t(bsx_handle h, uint64_t max_t) {
 inline void set_first(DevSpace& sp, const bsx_index* first) {
     for (int w = 0; w < 4; ++w) sp.first_digits[w] = first->init_digits[w];
     sp.first_variant = first->variant;
-}
-
-// first + delta as a problem index: the digits at or above n_any carry into the variant number (batching.py:212-255)
-inline bsx_index index_plus(const bsx_index& first, u128 delta, uint32_t n_any) {
-    bsx_index r = first;
-    u128 carry = 0;
-    for (int w = 0; w < 4; ++w) {
-        carry += r.init_digits[w];
-        carry += (uint64_t)delta;
-        delta >>= 64;
-        r.init_digits[w] = (uint64_t)carry;
-        carry >>= 64;
-    }
-    if (n_any < 256) {
-        uint64_t over = 0;
-        for (uint32_t b = n_any; b < 256 && b < n_any + 64; ++b) {
-            over |= ((r.init_digits[b >> 6] >> (b & 63)) & 1ull) << (b - n_any);
-            r.init_digits[b >> 6] &= ~(1ull << (b & 63));
-        }
-        for (uint32_t b = n_any + 64; b < 256; ++b) r.init_digits[b >> 6] &= ~(1ull << (b & 63));   // (check_range: none set)
-        r.variant += over;
-    }
-    return r;
 }
 
 inline double now_ms() {

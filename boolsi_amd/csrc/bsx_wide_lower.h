@@ -8,15 +8,10 @@
 #include <vector>
 
 #include "bsx.h"
+#include "bsx_lower_status.h"
 #include "bsx_wide.h"
 
 namespace bsx {
-
-struct LowerStatus {        // BSX_OK, or the status and the text for bsx_last_error
-    int status = BSX_OK;
-    const char* msg = "";
-    explicit operator bool() const { return status != BSX_OK; }
-};
 
 // bsx_set_network's arrays: monotone offsets, at most BSX_MAX_PREDECESSORS ascending predecessors, ceil(2^k / 64) table words
 LowerStatus check_network_arrays(uint32_t n_nodes, const uint32_t* pred_offsets, const uint32_t* pred_idx, const uint32_t* tt_word_offsets);

@@ -123,3 +123,34 @@ def test_target_cube_passes_equal_plain_counting_on_random_spaces(eng, seed, mon
     monkeypatch.setenv('BSX_CUBES', '0')
     b = eng.target_summary(first, count, max_t, mask, code, hist_bins=64, cap=cap)
     assert a[0] == b[0] and a[1].tolist() == b[1].tolist() and a[2].tobytes() == b[2].tobytes(), text
+
+
+def test_launch_count_equals_the_counting_plan(eng, monkeypatch):
+    """Ties the host's counting plan (bsx_lane_lower.h: count_piece; modelled in test_lane_lower_host.py) to what runs:
+    18 identity 'any' nodes, one radix-2 fixed-node variation, a range from digit 100 of variant 0 to digit 2^16 + 5 of
+    variant 1.  Every piece of the plan is one launch, whether or not its block is admitted as a cube pass."""
+    from oracle.cpu_oracle import Oracle
+    from test_lane_lower_host import count_plan
+    n, n_any = 20, 18
+    tnodes = (1, 7, 19)
+    text = synth.network_yaml(n, 2, 4242, initial={18: '0', 19: '1'}, fixed={18: 'any'},
+                              target={i: ('1' if i in tnodes else 'any') for i in range(n)})
+    cfg = parse_input_text(text, 64, Mode.TARGET)
+    net, space = compile_problem(cfg)
+    assert space.n_problems == 2 << n_any
+    eng.set_problem(net, space)
+    mask, code = target_words(cfg, net)
+    first, count, bins = 100, (1 << n_any) - 100 + (1 << 16) + 5, 8
+    plan = count_plan(first, 0, count, n_any, True)
+    assert [p[0] for p in plan] == ['plain', 'block', 'block', 'block', 'plain'] and len(plan) == 5
+    assert [(p[3], p[4]) for p in plan if p[0] == 'block'] == [(16, 0), (17, 0), (16, 1)] and plan[-1][2] == 5
+    monkeypatch.setenv('BSX_CUBES', '1')
+    a = eng.target_summary(first, count, 64, mask, code, hist_bins=bins, cap=0)
+    monkeypatch.setenv('BSX_CUBES', '0')
+    b = eng.target_summary(first, count, 64, mask, code, hist_bins=bins, cap=0)
+    assert a[3]['kernel_launches'] == len(plan) and b[3]['kernel_launches'] == 1
+    pp, _ = Oracle(net, space).target(first, count, 64, mask, code, n_threads=CORES)
+    reached = pp['reached'] != 0
+    expect = np.bincount(np.minimum(pp['t_stop'][reached], bins - 1).astype(np.int64), minlength=bins)
+    for total, hist, _, _ in (a, b):
+        assert total == int(reached.sum()) and hist.tolist() == expect.tolist()

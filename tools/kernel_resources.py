@@ -8,7 +8,7 @@ Register / spill / scratch report of every gfx950 kernel of the engine, from the
                                                             (only the files whose name starts with the argument)
 
 Columns: file, kernel (demangled), vgprs, agprs, sgprs, sgpr_spills, vgpr_spills, scratch_bytes_per_lane,
-occupancy_waves_per_simd, static_lds_bytes (the dynamic LDS is chosen at launch, bsx_api.cpp).
+occupancy_waves_per_simd, static_lds_bytes (the dynamic LDS is chosen at launch, bsx_lane_lower.cpp).
 `launched_by` marks the instantiations the BASELINE configs and the bench launch (tools/bench_configs.py).
 """
 import concurrent.futures
