@@ -110,6 +110,8 @@ extern "C" int bsx_destroy(bsx_handle h) {
     if (h->h_leaf) (void)hipHostFree(h->h_leaf);
     for (hipEvent_t e : h->ev_chain) (void)hipEventDestroy(e);
     for (hipStream_t st : h->side) if (st) (void)hipStreamDestroy(st);
+    if (h->top2) (void)hipStreamDestroy(h->top2);
+    if (h->ev_top2) (void)hipEventDestroy(h->ev_top2);
     if (h->ev_top0) (void)hipEventDestroy(h->ev_top0);
     if (h->ev_top1) (void)hipEventDestroy(h->ev_top1);
     if (h->stream) (void)hipStreamDestroy(h->stream);

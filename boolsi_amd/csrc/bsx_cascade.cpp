@@ -227,6 +227,7 @@ struct ChainBatch {
     Launch full{};
     uint64_t seg_cap = 0;
     uint32_t n_side = 0;            // sets of list buffers in use; > 1: lower levels on that many side streams
+    bool two_tops = false;          // the tops of consecutive chains alternate between the handle's stream and h->top2
 };
 
 // Mirror check + buffers for a batch of chains.  ok = false: the cached attractors do not fit the mirror (no cubes then).
@@ -266,12 +267,19 @@ int prepare_batch(bsx_handle h, const CascadeEnv& env, const std::vector<Chain*>
         if (B.n_side > 1 && !h->side[sl]) HIPCHK(h, hipStreamCreateWithFlags(&h->side[sl], hipStreamNonBlocking));
     }
     HIPCHK(h, h->d_unres.reserve((size_t)std::max(blocks, 1u) * kUnresCap * rec_words));
+    // two tops side by side list into two slots' segments: only with side streams (one slot = one stream, everything in order)
+    B.two_tops = h->knobs.cube_top_streams == 2 && B.n_side > 1;
+    if (B.two_tops && !h->top2) {
+        HIPCHK(h, hipStreamCreateWithFlags(&h->top2, hipStreamNonBlocking));
+        HIPCHK(h, hipEventCreateWithFlags(&h->ev_top2, hipEventDisableTiming));
+    }
     ok = true;
     return BSX_OK;
 }
 
 // The launches of one chain, enqueued on the handle's stream (nothing is waited for).
-// With side streams (B.n_side > 1) only the top level runs on the handle's stream; the lower levels -- short launches that
+// With side streams (B.n_side > 1) only the top level runs on the handle's stream (or, every other chain, on the second top
+// stream: B.two_tops, so that a top's workgroups take the CUs the previous top's free); the lower levels -- short launches that
 // mostly wait on memory -- follow on side stream `slot`, next to the following chains' top levels.
 // slot_busy[slot] = the event behind the last chain that used the slot's list buffers.
 // Level i reads the list d_near_list[slot][(i - 1) & 1] and writes d_near_list[slot][i & 1] (a level must not write into the
@@ -280,7 +288,8 @@ int enqueue_chain(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, c
                   std::vector<hipEvent_t>& slot_busy) {
     const uint32_t nw = h->net.nw, rec_words = nw + 3;
     const bool side = B.n_side > 1 && ch.top > 1;
-    hipStream_t const main_st = h->stream, tail_st = side ? h->side[slot] : h->stream;
+    // (B.two_tops: the top of an odd chain on h->top2, which run_batch has put behind the fill and the first chain's image)
+    hipStream_t const main_st = (B.two_tops && (ch.index & 1u)) ? h->top2 : h->stream, tail_st = side ? h->side[slot] : h->stream;
     hipEvent_t* const ev = h->ev_chain.data() + 3 * (size_t)ch.index;       // top in, top out (= the hand-over), chain done
     if (side && slot_busy[slot]) HIPCHK(h, hipStreamWaitEvent(main_st, slot_busy[slot], 0));   // (the buffers' previous user has finished)
     AttractParams Q0 = env.P;
@@ -372,6 +381,9 @@ int evaluate_chain(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, 
             std::fprintf(stderr, "[bsx] cube 2^%u (%u digits free) at digit value %llu%s: depth %u%s, %u digits here (%u relevant), %llu classes, %llu near a cycle, %llu unresolved\n",
                          ch.c1.a, ch.c1.n_free, (unsigned long long)ch.c1.d_lo, ch.c1.fix_mask ? " [sub-block]" : "", l.depth, i == 0 ? " (top)" : l.per_parent ? " (per parent)" : "", l.k_bits, l.r_here,
                          (unsigned long long)classes, (unsigned long long)c.near_classes, (unsigned long long)c.straggler_classes);
+        if (h->knobs.debug && c.phase_max[0])       // (BSX_DIAG build; workgroups that left before staging count in neither)
+            std::fprintf(stderr, "[bsx]   diag: depth %u prologue / loop / epilogue, us summed over workgroups %.1f / %.1f / %.1f, slowest %.1f / %.1f / %.1f\n", l.depth,
+                         c.phase_sum[0] / 100.0, c.phase_sum[1] / 100.0, c.phase_sum[2] / 100.0, c.phase_max[0] / 100.0, c.phase_max[1] / 100.0, c.phase_max[2] / 100.0);
         if (h->knobs.debug && l.per_parent) {
             const LeafProgram& prog = h->h_leaf[ch.index];
             std::fprintf(stderr, "[bsx] per-parent level: kb %u, %u enumerated rules, %u free rules, m %u\n", prog.kb, prog.n_enum, prog.n_free, prog.m);
@@ -456,6 +468,13 @@ int run_batch(bsx_handle h, const CascadeEnv& env, const CascadeShape& sh, const
             if (ch->lv.empty()) continue;
             const uint32_t slot = (B.n_side > 1 && ch->top > 1) ? n_listing++ % B.n_side : 0u;
             if (int rc = enqueue_chain(h, env, sh, B, *ch, slot, slot_busy)) return rc;
+            // the second top stream starts behind the first chain's top-in event: the fill, and the mirror image if that chain
+            // had to rebuild it (ensure_mirror_image launches on the handle's stream, in front of that event)
+            if (B.two_tops && ch->index == 0) HIPCHK(h, hipStreamWaitEvent(h->top2, h->ev_chain[0], 0));
+        }
+        if (B.two_tops) {                               // join: tops without lower levels end on their own stream
+            HIPCHK(h, hipEventRecord(h->ev_top2, h->top2));
+            HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_top2, 0));
         }
         for (hipEvent_t e : slot_busy) if (e) HIPCHK(h, hipStreamWaitEvent(h->stream, e, 0));      // join
     }

@@ -99,6 +99,8 @@ struct bsx_engine {
     bsx::DevBuf<uint32_t> d_near_seg[bsx::kSideStreams];        // classes listed for the level below, one segment per workgroup,
     bsx::DevBuf<uint32_t> d_near_list[bsx::kSideStreams][2];    // and the packed lists, alternated by level (one is read, one written)
     hipStream_t side[bsx::kSideStreams] = {};
+    hipStream_t top2 = nullptr;         // BSX_CUBE_TOP_STREAMS=2: the tops of a batch's odd chains (created on first use)
+    hipEvent_t ev_top2 = nullptr;       // ... fork (behind the fill and the image) and join
     bsx::DevBuf<uint32_t> d_unres;      // cascade: unresolved classes per level (state, t, member count)
     bsx::DevBuf<bsx::LeafProgram> d_leaf;   // cascade: the depth-1 level's per-parent program (bsx_device.h)
     bsx::LeafProgram* h_leaf = nullptr;     // ... its pinned staging copy

@@ -37,6 +37,7 @@ Knobs Knobs::from_env() {
     if (const char* e = std::getenv("BSX_CUBE_NEAR_CAP")) k.cube_near_cap = (uint64_t)std::max(1, std::atoi(e));
     const char* streams = std::getenv("BSX_CUBE_STREAMS");
     k.cube_streams = std::max(1, std::min((int)kSideStreams, streams ? std::atoi(streams) : (int)kSideStreams));
+    k.cube_top_streams = starts_with("BSX_CUBE_TOP_STREAMS", '1') ? 1 : 2;
     k.cube_split = zero_or_one("BSX_CUBE_SPLIT");
     k.sliced = zero_or_one("BSX_SLICED");
     k.wide = starts_with("BSX_WIDE", '1');

@@ -29,6 +29,8 @@ struct Knobs {
     uint32_t cube_depth = 0;        // BSX_CUBE_DEPTH: deepest top level, 1 .. kMaxCubeLevels; set = "fewest digits" rule (0 = not set)
     uint64_t cube_near_cap = 0;     // BSX_CUBE_NEAR_CAP: classes per hand-over segment, at least 1 (0 = not set)
     int cube_streams = 0;           // BSX_CUBE_STREAMS: side streams of a batch, 1 .. kSideStreams (default: all)
+    int cube_top_streams = 2;       // BSX_CUBE_TOP_STREAMS=1: every top on the handle's stream (default 2: the tops of consecutive chains
+                                    // alternate between two streams; needs side streams, so BSX_CUBE_STREAMS=1 implies 1)
     int cube_split = -1;            // BSX_CUBE_SPLIT: 0 no sub-blocks, 1 split whatever the size (-1 = the estimate decides)
     int sliced = -1;                // BSX_SLICED: 0 per-lane simulate kernel, 1 first-generation sliced kernel (-1 = by shape)
     bool wide = false;              // BSX_WIDE=1: the wide-state family for every network
