@@ -123,13 +123,17 @@ def table_from_merged(merged, dtype):
     return out
 
 
-def run_attract_range(engine, first, count, max_t=inf, max_attractor_l=inf, cap=1 << 20):
+def run_attract_range(engine, first, count, max_t=inf, max_attractor_l=inf, cap=1 << 20, sampled=False, seed=0):
     """Engine over [first, first+count) -> (merged dict, n_no_attractor, stats dict).  ONE engine call however large
     the range (bsx_run_attract2: 128-bit index and count, wide sums), as one attract_master run covers the
-    reference's whole N (attract.py:67-230); ranges beyond 2^128 problems are cut into calls of 2^127."""
+    reference's whole N (attract.py:67-230); ranges beyond 2^128 problems are cut into calls of 2^127.
+    sampled: [first, first+count) are sample numbers of `seed` (bsx_run_attract_sampled), not problem indices."""
     merged_tables, none = [], 0
     stats = {'problems': 0, 'state_steps': 0, 'executed_steps': 0, 'kernel_ms': 0.0, 'total_ms': 0.0,
              'kernel_launches': 0}
+    if sampled:
+        r = engine.attract_sampled(seed, first, count, max_t, max_attractor_l, cap=cap)
+        return merge_tables([r.table]), r.n_no_attractor, {k: r.stats[k] for k in stats}
     done = 0
     while done < count:
         piece = min(count - done, 1 << 127)
@@ -145,9 +149,11 @@ def run_attract_range(engine, first, count, max_t=inf, max_attractor_l=inf, cap=
 
 def attract_master(engine, origin_simulation_problem, simulation_problem_variations,
                    predecessor_node_lists, truth_tables, max_t, max_attractor_l,
-                   n_simulation_problems, comm=None, with_states=True, with_activity=False):
+                   n_simulation_problems, comm=None, with_states=True, with_activity=False, samples=None, seed=0):
     """
     Attract over the whole problem space, range-partitioned over `comm` (one rank per GPU).
+    samples = N: over samples 0 .. N - 1 of `seed` instead (include/bsx.h defines them), range-partitioned in the
+    same way; frequencies, shares and the log lines then refer to the N samples.
     Returns (list of AggregatedAttractor in final order, n_no_attractor, total_frequency, stats);
     identical on every rank.  Log lines follow attract.py:95-138.
     with_states / with_activity: list every attractor's states / its nodes' mean activity (what the node
@@ -156,6 +162,11 @@ def attract_master(engine, origin_simulation_problem, simulation_problem_variati
     comm = comm or Comm()
     log = logging.getLogger()
     n_processes_text = '{} GPU processes'.format(comm.world) if comm.world > 1 else 'Single process'
+    sampled = samples is not None
+    if sampled:
+        if comm.rank == 0:
+            log.info('Sampling {} initial conditions out of {} with seed {}.'.format(samples, n_simulation_problems, seed))
+        n_simulation_problems = samples
     if comm.rank == 0:
         log.info('{} will be used to find attractors from {} initial conditions...'.format(
             n_processes_text, n_simulation_problems))
@@ -164,11 +175,11 @@ def attract_master(engine, origin_simulation_problem, simulation_problem_variati
     space = compile_space(origin_simulation_problem, simulation_problem_variations)
     engine.set_problem(net, space)
     first, count = partition(n_simulation_problems, comm.world, comm.rank)
-    merged, none, stats = run_attract_range(engine, first, count, max_t, max_attractor_l)
+    merged, none, stats = run_attract_range(engine, first, count, max_t, max_attractor_l, sampled=sampled, seed=seed)
 
     if comm.active:
         from . import _lib
-        tables = comm.allgather_records(table_from_merged(merged, _lib.ATTR_REC2W if getattr(engine, 'wide', False) else _lib.ATTR_REC2))
+        tables = comm.allgather_records(table_from_merged(merged, _lib.ATTR_REC2W if sampled or getattr(engine, 'wide', False) else _lib.ATTR_REC2))
         merged = merge_tables(tables)
         none, steps, execd = comm.allreduce_sum_int([none, stats['state_steps'], stats['executed_steps']])
         stats['state_steps'], stats['executed_steps'] = steps, execd

@@ -173,7 +173,14 @@ def simulate(**kw):
 @click.option('--transitions', 'transitions', is_flag=True,
               help='Also flip every free node once in every state of every attractor found and write where the '
                    'network goes to attractor_transitions.csv.')
+@click.option('--samples', 'samples', type=click.IntRange(min=1),
+              help='Find attractors from this many sampled initial conditions (and variations) instead of all of them: '
+                   'for problem spaces too large to enumerate. Frequencies are shares of the sample.')
+@click.option('--seed', 'seed', type=click.IntRange(min=0, max=2 ** 64 - 1), default=None,
+              help='Seed of --samples: the same seed gives the same sample. Defaults to 0. An error without --samples.')
 def attract(**kw):
+    if kw['seed'] is not None and kw['samples'] is None:
+        raise click.UsageError('--seed needs --samples: without --samples every initial condition is enumerated.')
     def body(run):
         from .attract import attract_master, profile_attractors
         from .attractor_analysis import find_node_correlations, uses_device
@@ -191,7 +198,8 @@ def attract(**kw):
             engine, cfg['origin simulation problem'], cfg['simulation problem variations'],
             cfg['incoming node lists'], cfg['truth tables'], max_t, max_len,
             cfg['total combination count'], comm=run.comm, with_states=not kw['no_attractor_output'],
-            with_activity=not kw['no_node_correlations'] and not kw['no_attractor_output'])
+            with_activity=not kw['no_node_correlations'] and not kw['no_attractor_output'],
+            samples=kw['samples'], seed=kw['seed'] or 0)
         if run.comm.rank != 0:
             return
         logging.getLogger().info(
@@ -208,7 +216,7 @@ def attract(**kw):
         if not kw['no_attractor_output']:
             _, fixed_nodes, _ = cfg['origin simulation problem']
             output_attractors(attractors, total_frequency, fixed_nodes, cfg['node names'],
-                              cfg['total combination count'], max_len, max_t, run.out)
+                              kw['samples'] or cfg['total combination count'], max_len, max_t, run.out)
         if kw['transitions']:
             from .attractor_analysis import attractor_transitions
             from .output import output_attractor_transitions

@@ -117,6 +117,7 @@ extern "C" int bsx_destroy(bsx_handle h) {
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->h_ctr) (void)hipHostFree(h->h_ctr);
     wide_release(h);
+    wide_release_sample(h);
     delete h;
     return BSX_OK;
 }
@@ -154,6 +155,7 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     if (n_nodes == 0 || !pred_offsets || !tt_word_offsets || !tt_words)
         return fail(h, BSX_ERR_INVALID, "bsx_set_network: null table or zero nodes");
     h->knobs = Knobs::from_env();
+    wide_release_sample(h);
     if (n_nodes > BSX_MAX_NODES || h->knobs.wide)          // the wide-state family (bsx_wide_host.h)
         return wide_set_network(h, n_nodes, pred_offsets, pred_idx, tt_word_offsets, tt_words);
     wide_release(h);
@@ -162,6 +164,13 @@ extern "C" int bsx_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* p
     h->have_space = false;
 
     if (const LowerStatus s = check_network_arrays(n_nodes, pred_offsets, pred_idx, tt_word_offsets)) return fail(h, s.status, s.msg);
+    {   // the arrays as received: the sampled calls lower them onto the wide family (bsx_sample_api.cpp)
+        SampleInputs& in = h->inputs;
+        in.pred_offsets.assign(pred_offsets, pred_offsets + n_nodes + 1);
+        in.pred_idx.assign(pred_idx, pred_idx + pred_offsets[n_nodes]);
+        in.tt_word_offsets.assign(tt_word_offsets, tt_word_offsets + n_nodes + 1);
+        in.tt_words.assign(tt_words, tt_words + tt_word_offsets[n_nodes]);
+    }
     LaneNet L;
     lane_lower_network(n_nodes, pred_offsets, pred_idx, tt_word_offsets, tt_words, h->knobs.cache_lds_kb, h->knobs.lut_mode, L, h->model);
     const uint32_t nw = L.nw, k_mux = L.k_mux;
@@ -219,6 +228,7 @@ extern "C" int bsx_set_problem_space(bsx_handle h, const uint64_t* origin_state_
     if (!origin_state_words) return fail(h, BSX_ERR_INVALID, "origin state is null");
     if (n_pert_var > BSX_MAX_PERT_VARIATIONS) return fail(h, BSX_ERR_UNSUPPORTED, "more than BSX_MAX_PERT_VARIATIONS perturbation variations");
     if (n_any > h->n_nodes) return fail(h, BSX_ERR_INVALID, "more 'any' nodes than nodes");
+    wide_release_sample(h);
     if (h->wide)
         return wide_set_problem_space(h, origin_state_words, any_nodes, n_any, fixed, n_fixed, fixed_var, n_fixed_var,
                                       sched, n_sched, pert_var, n_pert_var);
@@ -228,6 +238,15 @@ extern "C" int bsx_set_problem_space(bsx_handle h, const uint64_t* origin_state_
     if (const LowerStatus s = lane_lower_space(h->n_nodes, h->net.nw, h->w64, origin_state_words, any_nodes, n_any, fixed, n_fixed,
                                                fixed_var, n_fixed_var, sched, n_sched, pert_var, n_pert_var, S))
         return fail(h, s.status, s.msg);
+    {   // the arguments as received, for the sampled calls' second lowering
+        SampleInputs& in = h->inputs;
+        in.origin.assign(origin_state_words, origin_state_words + h->w64);
+        in.any_nodes.assign(any_nodes, any_nodes + n_any);
+        in.fixed.assign(fixed, fixed + n_fixed);
+        in.fixed_var.assign(fixed_var, fixed_var + n_fixed_var);
+        in.sched.assign(sched, sched + n_sched);
+        in.pert_var.assign(pert_var, pert_var + n_pert_var);
+    }
     h->model.sched = S.sched;
     h->model.any = S.any;
     h->model.fv = S.fv;

@@ -1,6 +1,6 @@
 // Host-side internals shared by the translation units behind include/bsx.h (bsx_api.cpp, bsx_target_api.cpp,
 // bsx_simulate_api.cpp, bsx_attract_api.cpp, bsx_cascade.cpp, bsx_fgraph_api.cpp, bsx_wide_api.cpp, bsx_wide_attract_api.cpp, bsx_wide_trans_api.cpp,
-// bsx_comm.cpp): the engine handle, device buffers, error plumbing.  Not part of the ABI.
+// bsx_sample_api.cpp, bsx_comm.cpp): the engine handle, device buffers, error plumbing.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,6 +47,16 @@ struct ProfileKeep {
     DevBuf<uint64_t> keys, lengths, offsets, states;
     DevBuf<uint8_t> closed;
     uint32_t launches = 0;
+};
+
+// host copies of the arguments of bsx_set_network / bsx_set_problem_space (HostModel holds only the first table word)
+struct SampleInputs {
+    std::vector<uint32_t> pred_offsets, pred_idx, tt_word_offsets, any_nodes;
+    std::vector<uint64_t> tt_words, origin;
+    std::vector<bsx_fixed> fixed;
+    std::vector<bsx_fixed_var> fixed_var;
+    std::vector<bsx_pert> sched;
+    std::vector<bsx_pert_var> pert_var;
 };
 
 }  // namespace bsx
@@ -147,6 +157,11 @@ struct bsx_engine {
 
     // wide-state family (bsx_wide_host.h, bsx_wide_*api.cpp): set when the network has more than BSX_MAX_NODES nodes or BSX_WIDE=1
     bsx::WideHost* wide = nullptr;
+    // sampled calls on a handle of the <= BSX_MAX_NODES family (bsx_sample_api.cpp): what bsx_set_network and
+    // bsx_set_problem_space received, and their second lowering onto the wide family, built on the first sampled call and
+    // dropped by the next bsx_set_network / bsx_set_problem_space
+    bsx::SampleInputs inputs;
+    bsx::WideHost* sample_wide = nullptr;
 
     // RCCL communicator of this handle's rank (bsx_comm.cpp); librccl is loaded on first use
     void* comm = nullptr;       // ncclComm_t
@@ -165,6 +180,7 @@ struct bsx_engine {
 
 namespace bsx {
 void wide_release(bsx_handle h);
+void wide_release_sample(bsx_handle h);
 int wide_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* pred_offsets, const uint32_t* pred_idx,
                      const uint32_t* tt_word_offsets, const uint64_t* tt_words);
 int wide_set_problem_space(bsx_handle h, const uint64_t* origin_state_words, const uint32_t* any_nodes, uint32_t n_any,

@@ -77,6 +77,10 @@ inline Launch plan_persistent(const bsx_engine* h, uint64_t count, size_t shmem)
 
 // bsx_lane_lower.h's range_check against the handle's problem space
 inline int check_range(bsx_handle h, const bsx_index* first, u128 count) {
+    // (a wide space with more 'any' nodes than a bsx_index holds is for the sampled calls alone: whatever the index says,
+    // a call that enumerates is refused before the index is looked at)
+    if (h->wide && h->sp.n_any > 64 * BSX_MAX_WORDS)
+        return fail(h, BSX_ERR_UNSUPPORTED, "more 'any' nodes than a bsx_index holds (64 * BSX_MAX_WORDS)");
     const LowerStatus s = range_check(first, count, h->sp.n_any, h->variant_count, h->variant_count_saturated);
     return s ? fail(h, s.status, s.msg) : BSX_OK;
 }

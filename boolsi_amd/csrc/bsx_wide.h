@@ -60,6 +60,26 @@ struct WideParams {
     uint64_t max_len;
     uint32_t* x0;               // scratch: [gridDim.x][rows * L] s(T_p) of the group
     unsigned long long* ctr;    // [0] reference steps, [1] executed trajectory updates, [2] step-limit hits
+    // sampled source (k_wide<K, KW, true> only; behind every field the other kernels read, so that their offsets stay)
+    uint64_t sample_k0;         // sample_k0(seed)
+    uint64_t sample_first;      // first sample of this launch
+    uint64_t sample_variants;   // V, the space's variant count (not saturated)
+};
+
+// ---- sampled problem source (k_wide_sampled / k_sample_problems in bsx_wide.hip, bsx_sample.h has the definition) ----
+// k_wide<K, KW, true> is k_wide's attract branch over samples [sample_first, sample_first + count) of a seed: trajectory k
+// of a group is sample sample_first + base + k.  Only a group's set-up differs (s(0) and the variant number come from the
+// generator, word by word, not from a decoded index); first_digits / first_variant / offsets are not read.
+// k_sample_problems: s(0) and the variant number of listed samples, one thread per sample
+struct WideSampleListParams {
+    uint32_t n_nodes, w64, n_any, pad;
+    uint32_t origin[kWideMaxW32];   // origin state ('any' nodes cleared)
+    const uint32_t* any_nodes;      // [n_any]
+    uint64_t k0, variant_count;
+    const uint64_t* samples;        // [n]
+    uint64_t n;
+    uint64_t* states;               // [n][w64]
+    uint64_t* variants;             // nullable: [n]
 };
 
 // ---- attractor profile (k_wide_profile in bsx_wide.hip, bsx_run_attractor_profile) ----

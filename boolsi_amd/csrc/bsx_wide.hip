@@ -9,10 +9,13 @@
 //   * mu: a second lock-step pass, y = s(T_p + lambda_b) (bit b frozen after lambda_b steps) against x = s(T_p);
 //   * key: the minimum state over one lap of the cycle, by a bit-sliced lexicographic compare from the highest
 //     row down (per-slice lt / eq masks, combined across slices from the top).
+// k_wide_sampled is the attract branch over samples of a seed instead of consecutive problem indices (bsx_sample.h):
+// the same body, with the group's set-up chosen at compile time.
 #include <hip/hip_runtime.h>
 
 #include "bsx_device.h"
 #include "bsx_planes.h"
+#include "bsx_sample.h"
 #include "bsx_trans.h"
 #include "bsx_wide.h"
 #include "bsx_wtrans.h"
@@ -117,10 +120,18 @@ __device__ __forceinline__ uint64_t wide_gather64(const WideParams& P, const uin
     return word;
 }
 
+// Sampled source: the block keys of column cw (first sample j0), as the group's set-up left them in `keys` (4 words per column)
+__device__ __forceinline__ SampleColumn wide_sample_column(const uint32_t* keys, uint32_t cw, uint64_t j0) {
+    return SampleColumn{(uint64_t)keys[4 * cw] | ((uint64_t)keys[4 * cw + 1] << 32),
+                        (uint64_t)keys[4 * cw + 2] | ((uint64_t)keys[4 * cw + 3] << 32), (uint32_t)(j0 & 63u)};
+}
+
 }  // namespace
 
 // KW: the network has nodes with more than 6 predecessors (their path's 32 table indices cost registers)
-template <int K, bool KW>
+// SAMPLED: trajectory k of a group is sample P.sample_first + base + k of the seed behind P.sample_k0 (bsx_sample.h), not
+// problem first + base + k; attract only.  A compile-time choice: it changes a group's set-up and nothing behind it.
+template <int K, bool KW, bool SAMPLED = false>
 __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
     WideCtx X;
@@ -157,41 +168,69 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
         }
         for (uint32_t i = tid; i < 2 * (P.n_fslots + P.n_pv) * L; i += kWideThreads) fmv[i] = 0;
         if (tid < 8) misc[tid] = 0;
+        if constexpr (SAMPLED) {
+            // the block keys of column tid's 32 samples (at most two blocks), once per group: col[4 tid ..], free until the warm-up
+            if (tid < L) {
+                const SampleColumn sc = sample_column(P.sample_k0, P.sample_first + base + 32ull * tid);
+                col[4 * tid + 0] = (uint32_t)sc.kb0; col[4 * tid + 1] = (uint32_t)(sc.kb0 >> 32);
+                col[4 * tid + 2] = (uint32_t)sc.kb1; col[4 * tid + 3] = (uint32_t)(sc.kb1 >> 32);
+            }
+        }
         __syncthreads();
+        if constexpr (SAMPLED) {
+            // s(0): one word per ('any' ordinal, column), one plain store each (the origin has these rows cleared and
+            // 'any' rows are distinct)
+            for (uint32_t i = tid; i < P.n_any * L; i += kWideThreads) {
+                const uint32_t a = i >> P.lshift, cw = i & (L - 1);
+                const SampleColumn sc = wide_sample_column(col, cw, P.sample_first + base + 32ull * cw);
+                const uint32_t n_bits = n_valid > 32 * cw ? (n_valid - 32 * cw < 32u ? n_valid - 32 * cw : 32u) : 0u;
+                B[0][P.any_nodes[a] * L + cw] = sample_column_word(sc, a, n_bits);
+            }
+        }
         for (uint32_t k = tid; k < G; k += kWideThreads) {
             uint32_t tp = P.tp_origin, st = ST_ACTIVE;
             if (k >= n_valid) {
                 st = ST_INVALID;
             } else {
-                uint64_t p = base + k;
-                if (P.offsets) p = P.offsets[p];
-                // digits = first_digits + p; what spills over bit n_any goes to the variant number
-                uint64_t d[5];
-                unsigned long long carry = p;
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned long long a = P.first_digits[w], sum = a + carry;
-                    carry = (sum < a) ? 1ull : 0ull;
-                    d[w] = sum;
-                }
-                d[4] = carry;
-                const uint32_t sw = P.n_any >> 6, sb = P.n_any & 63;
-                uint64_t lo = d[0], hi = d[1];      // words sw, sw + 1 (selects: the array stays in registers)
+                uint64_t variant;
+                uint32_t bit, cw;
+                if constexpr (SAMPLED) {
+                    // sample first + base + k: the variant number is one draw of its own (the state bits are stored above)
+                    bit = 1u << (k & 31u); cw = k >> 5;
+                    const SampleColumn sc = wide_sample_column(col, cw, P.sample_first + base + 32ull * cw);
+                    variant = sample_variant(sample_u(sample_column_key(sc, k & 31u), P.n_any, sample_column_lane(sc, k & 31u)),
+                                             P.sample_variants);
+                } else {
+                    uint64_t p = base + k;
+                    if (P.offsets) p = P.offsets[p];
+                    // digits = first_digits + p; what spills over bit n_any goes to the variant number
+                    uint64_t d[5];
+                    unsigned long long carry = p;
+                    for (int w = 0; w < 4; ++w) {
+                        const unsigned long long a = P.first_digits[w], sum = a + carry;
+                        carry = (sum < a) ? 1ull : 0ull;
+                        d[w] = sum;
+                    }
+                    d[4] = carry;
+                    const uint32_t sw = P.n_any >> 6, sb = P.n_any & 63;
+                    uint64_t lo = d[0], hi = d[1];      // words sw, sw + 1 (selects: the array stays in registers)
 #pragma unroll
-                for (int w = 1; w < 5; ++w) {
-                    lo = (sw == (uint32_t)w) ? d[w] : lo;
-                    hi = (sw + 1 == (uint32_t)w) ? d[w] : hi;
-                }
-                if (sw >= 4) hi = 0;
-                const uint64_t over = sb ? ((lo >> sb) | (hi << (64 - sb))) : lo;
-                uint64_t variant = P.first_variant + over;
-                const uint32_t bit = 1u << (k & 31u), cw = k >> 5;
-                uint64_t sh[4] = {d[0], d[1], d[2], d[3]};
-                for (uint32_t j = 0; j < P.n_any; ++j) {
-                    if (sh[0] & 1u) atomicOr(&B[0][P.any_nodes[j] * L + cw], bit);
-                    sh[0] = (sh[0] >> 1) | (sh[1] << 63);
-                    sh[1] = (sh[1] >> 1) | (sh[2] << 63);
-                    sh[2] = (sh[2] >> 1) | (sh[3] << 63);
-                    sh[3] >>= 1;
+                    for (int w = 1; w < 5; ++w) {
+                        lo = (sw == (uint32_t)w) ? d[w] : lo;
+                        hi = (sw + 1 == (uint32_t)w) ? d[w] : hi;
+                    }
+                    if (sw >= 4) hi = 0;
+                    const uint64_t over = sb ? ((lo >> sb) | (hi << (64 - sb))) : lo;
+                    variant = P.first_variant + over;
+                    bit = 1u << (k & 31u); cw = k >> 5;
+                    uint64_t sh[4] = {d[0], d[1], d[2], d[3]};
+                    for (uint32_t j = 0; j < P.n_any; ++j) {
+                        if (sh[0] & 1u) atomicOr(&B[0][P.any_nodes[j] * L + cw], bit);
+                        sh[0] = (sh[0] >> 1) | (sh[1] << 63);
+                        sh[1] = (sh[1] >> 1) | (sh[2] << 63);
+                        sh[2] = (sh[2] >> 1) | (sh[3] << 63);
+                        sh[3] >>= 1;
+                    }
                 }
                 for (uint32_t j = 0; j < P.n_fv; ++j) {
                     const uint32_t range = P.fv[3 * j + 1], slot = P.fv[3 * j + 2];
@@ -226,7 +265,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
         uint32_t* nxt = B[1];
         uint64_t group_steps = 0;
 
-        if (P.mode == kWideSimulate) {
+        if (!SAMPLED && P.mode == kWideSimulate) {           // (the sampled source serves attract only)
             // ---- s(0 .. T): trajectories as they pass, digest accumulators X / Y per row in B[2] / B[3]
             uint64_t T = P.max_t;
             if (P.t_len) {
@@ -283,7 +322,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
                 for (uint32_t k = 0; k < n_valid; ++k) ref += P.t_len ? P.t_len[base + k] : P.max_t;
                 steps_ref += ref;
             }
-        } else if (P.mode == kWideTarget) {
+        } else if (!SAMPLED && P.mode == kWideTarget) {
             // ---- first t >= T_p with s(t) & mask == code (target.py:109-133); a trajectory whose cycle has closed
             //      (Brent from T_max = max T_p of the group, when every trajectory is autonomous) has shown all its
             //      states and ends without a hit
@@ -522,6 +561,54 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
     if (steps_ref) atomicAdd(&P.ctr[0], steps_ref);
     if (tid == 0 && steps_exec) atomicAdd(&P.ctr[1], steps_exec);
     if (limit_hits) atomicAdd(&P.ctr[2], limit_hits);
+}
+
+// s(0) as w64 words and the variant number of the listed samples (bsx_sample_problems): one thread per sample, which
+// owns its w64 output words.
+__global__ __launch_bounds__(256) void k_sample_problems(const WideSampleListParams Q) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= Q.n) return;
+    const uint64_t j = Q.samples[q];
+    const uint64_t kb = sample_block_key(Q.k0, j >> 6);
+    uint64_t* out = Q.states + q * Q.w64;
+    // 'any' nodes are ascending (wide_lower_space), so one pass over them fills the words in order: each word is built
+    // in a register and stored once
+    uint32_t a = 0;
+    for (uint32_t w = 0; w < Q.w64; ++w) {
+        uint64_t word = (uint64_t)Q.origin[2 * w] | ((uint64_t)Q.origin[2 * w + 1] << 32);
+        for (; a < Q.n_any && (Q.any_nodes[a] >> 6) == w; ++a)
+            if (sample_any_bit(kb, a, j)) word |= 1ull << (Q.any_nodes[a] & 63u);
+        out[w] = word;
+    }
+    if (Q.variants) Q.variants[q] = sample_variant_of(kb, Q.n_any, j, Q.variant_count);
+}
+
+hipError_t launch_sample_problems(const WideSampleListParams& Q, hipStream_t st) {
+    const uint64_t blocks = (Q.n + 255) / 256;
+    hipLaunchKernelGGL(k_sample_problems, dim3((uint32_t)blocks), dim3(256), 0, st, Q);
+    return hipGetLastError();
+}
+
+// attract over samples of a seed (bsx_run_attract_sampled): k_wide's attract branch behind the sampled set-up
+template <int K>
+static hipError_t launch_wide_sampled_k(dim3 grid, size_t shmem, hipStream_t st, const WideParams& Q) {
+    const void* fn = Q.wdesc ? (const void*)k_wide<K, true, true> : (const void*)k_wide<K, false, true>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return e;
+    void* args[] = {const_cast<WideParams*>(&Q)};
+    return hipLaunchKernel(fn, grid, dim3(kWideThreads), args, shmem, st);
+}
+
+hipError_t launch_wide_sampled(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& Q) {
+    switch (k) {
+        case 1: return launch_wide_sampled_k<1>(grid, shmem, st, Q);
+        case 2: return launch_wide_sampled_k<2>(grid, shmem, st, Q);
+        case 3: return launch_wide_sampled_k<3>(grid, shmem, st, Q);
+        case 4: return launch_wide_sampled_k<4>(grid, shmem, st, Q);
+        case 5: return launch_wide_sampled_k<5>(grid, shmem, st, Q);
+        case 6: return launch_wide_sampled_k<6>(grid, shmem, st, Q);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 template <int K>

@@ -15,6 +15,40 @@ void wide_release(bsx_handle h) {
     h->wide = nullptr;
 }
 
+// The second lowering of a handle of the <= BSX_MAX_NODES family (bsx_sample_api.cpp builds it on the first sampled call)
+void wide_release_sample(bsx_handle h) {
+    delete h->sample_wide;
+    h->sample_wide = nullptr;
+}
+
+int wide_upload_network(bsx_handle h, WideHost& W, uint32_t n_nodes, const uint32_t* pred_offsets, const uint32_t* pred_idx,
+                        const uint32_t* tt_word_offsets, const uint64_t* tt_words) {
+    wide_lower_network(n_nodes, pred_offsets, pred_idx, tt_word_offsets, tt_words, W.net);
+    HIPCHK(h, W.d_wdesc.upload(W.net.wdesc));
+    HIPCHK(h, W.d_wpreds.upload(W.net.wpreds));
+    HIPCHK(h, W.d_wtt.upload(W.net.wtt));
+    HIPCHK(h, W.d_ctr.alloc(4));
+    W.have_space = false;
+    return BSX_OK;
+}
+
+int wide_upload_space(bsx_handle h, WideHost& W, const uint64_t* origin_state_words, const uint32_t* any_nodes, uint32_t n_any,
+                      const bsx_fixed* fixed, uint32_t n_fixed, const bsx_fixed_var* fixed_var, uint32_t n_fixed_var,
+                      const bsx_pert* sched, uint32_t n_sched, const bsx_pert_var* pert_var, uint32_t n_pert_var) {
+    W.have_space = false;
+    WideSpace& S = W.space;
+    if (const LowerStatus s = wide_lower_space(W.net, origin_state_words, any_nodes, n_any, fixed, n_fixed, fixed_var, n_fixed_var,
+                                               sched, n_sched, pert_var, n_pert_var, S))
+        return fail(h, s.status, s.msg);
+    HIPCHK(h, W.d_desc.upload(S.desc));
+    HIPCHK(h, W.d_any.upload(S.any));
+    HIPCHK(h, W.d_fv.upload(S.fv));
+    HIPCHK(h, W.d_pv.upload(S.pv));
+    HIPCHK(h, W.d_sched.upload(S.sched));
+    W.have_space = true;
+    return BSX_OK;
+}
+
 int wide_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* pred_offsets, const uint32_t* pred_idx,
                      const uint32_t* tt_word_offsets, const uint64_t* tt_words) {
     if (const LowerStatus s = wide_check_size(n_nodes)) return fail(h, s.status, s.msg);
@@ -23,12 +57,7 @@ int wide_set_network(bsx_handle h, uint32_t n_nodes, const uint32_t* pred_offset
     if (const LowerStatus s = check_network_arrays(n_nodes, pred_offsets, pred_idx, tt_word_offsets)) return fail(h, s.status, s.msg);
     if (!h->wide) h->wide = new WideHost();
     WideHost& W = *h->wide;
-    wide_lower_network(n_nodes, pred_offsets, pred_idx, tt_word_offsets, tt_words, W.net);
-    HIPCHK(h, W.d_wdesc.upload(W.net.wdesc));
-    HIPCHK(h, W.d_wpreds.upload(W.net.wpreds));
-    HIPCHK(h, W.d_wtt.upload(W.net.wtt));
-    HIPCHK(h, W.d_ctr.alloc(4));
-    W.have_space = false;
+    if (int rc = wide_upload_network(h, W, n_nodes, pred_offsets, pred_idx, tt_word_offsets, tt_words)) return rc;
     h->n_nodes = n_nodes; h->w64 = W.net.w64;
     h->net = DevNet{};
     h->net.n_nodes = n_nodes; h->net.nw = (n_nodes + 31) / 32; h->net.k_mux = W.net.K;
@@ -41,36 +70,27 @@ int wide_set_problem_space(bsx_handle h, const uint64_t* origin_state_words, con
                            const bsx_fixed* fixed, uint32_t n_fixed, const bsx_fixed_var* fixed_var, uint32_t n_fixed_var,
                            const bsx_pert* sched, uint32_t n_sched, const bsx_pert_var* pert_var, uint32_t n_pert_var) {
     WideHost& W = *h->wide;
-    if (n_any > 64 * BSX_MAX_WORDS)
-        return fail(h, BSX_ERR_UNSUPPORTED, "more 'any' nodes than a bsx_index holds (64 * BSX_MAX_WORDS)");
+    // (up to n 'any' nodes: a space with more than a bsx_index holds, 64 * BSX_MAX_WORDS, is reached by the sampled calls
+    // alone; the enumerating calls refuse it: check_range of bsx_host.h, wide_check_enumerable)
     HIPCHK(h, hipSetDevice(h->device));
-    h->have_space = W.have_space = false;
-    WideSpace& S = W.space;
-    if (const LowerStatus s = wide_lower_space(W.net, origin_state_words, any_nodes, n_any, fixed, n_fixed, fixed_var, n_fixed_var,
-                                               sched, n_sched, pert_var, n_pert_var, S))
-        return fail(h, s.status, s.msg);
-    HIPCHK(h, W.d_desc.upload(S.desc));
-    HIPCHK(h, W.d_any.upload(S.any));
-    HIPCHK(h, W.d_fv.upload(S.fv));
-    HIPCHK(h, W.d_pv.upload(S.pv));
-    HIPCHK(h, W.d_sched.upload(S.sched));
+    h->have_space = false;
+    if (int rc = wide_upload_space(h, W, origin_state_words, any_nodes, n_any, fixed, n_fixed, fixed_var, n_fixed_var, sched, n_sched,
+                                   pert_var, n_pert_var))
+        return rc;
+    const WideSpace& S = W.space;
     // the fields of the handle that the range checks of bsx_host.h read
     h->sp = DevSpace{};
     h->sp.n_any = n_any;
     h->variant_count_saturated = S.variant_count_saturated; h->variant_count = S.variant_count; h->tp_max = S.tp_max;
-    h->have_space = W.have_space = true;
+    h->have_space = true;
     return BSX_OK;
 }
 
-// Enqueues one k_wide launch over [first, first + count) (count problems, or the listed offsets) on the engine's
-// stream and returns without waiting; the caller fills the parameter fields of the mode's sinks before.  The kernel
-// ADDS to the counters in W.d_ctr: the caller zeroes them once, in front of its first launch.
-int wide_enqueue(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t) {
-    WideHost& W = *h->wide;
+// Everything of a k_wide launch over `count` problems but their source: network, space, caps, counters, the attract scratch.
+// -> the launch's workgroups in *blocks_out.
+static int wide_fill_launch(bsx_handle h, WideHost& W, WideParams& P, uint64_t count, uint64_t max_t, uint64_t* blocks_out) {
     const WideSpace& S = W.space;
     wide_fill_net(W, P);
-    for (int w = 0; w < 4; ++w) P.first_digits[w] = first->init_digits[w];
-    P.first_variant = first->variant;
     std::memcpy(P.origin, S.origin, sizeof(P.origin));
     P.n_any = S.n_any; P.n_fv = S.n_fv; P.n_pv = S.n_pv; P.n_sched = S.n_sched;
     P.tp_origin = S.tp_origin;
@@ -80,23 +100,46 @@ int wide_enqueue(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t c
     P.cap_inf = max_t == BSX_T_INF ? 1u : 0u;
     P.step_limit = h->knobs.wide_step_limit;        // kWideStepLimit unless BSX_WIDE_STEP_LIMIT says less
     P.ctr = W.d_ctr.p;
-    const uint64_t blocks = wide_blocks(h, count, S.shmem);
+    const uint64_t blocks = wide_blocks(h, W, count, S.shmem);
     if (P.mode == kWideAttract) {
         // (grow-only: a chunked run's first launch is its largest, so the buffer never moves under a queued launch)
         HIPCHK(h, W.d_x0.reserve((size_t)blocks * W.net.rows * S.L));
         P.x0 = W.d_x0.p;
     }
-    HIPCHK(h, launch_wide((int)W.net.K, dim3((uint32_t)blocks), S.shmem, h->stream, P));
+    *blocks_out = blocks;
+    return BSX_OK;
+}
+
+// Enqueues one k_wide launch over [first, first + count) (count problems, or the listed offsets) on the engine's
+// stream and returns without waiting; the caller fills the parameter fields of the mode's sinks before.  The kernel
+// ADDS to the counters in W.d_ctr: the caller zeroes them once, in front of its first launch.
+int wide_enqueue(bsx_handle h, WideHost& W, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t) {
+    uint64_t blocks = 0;
+    if (int rc = wide_fill_launch(h, W, P, count, max_t, &blocks)) return rc;
+    for (int w = 0; w < 4; ++w) P.first_digits[w] = first->init_digits[w];
+    P.first_variant = first->variant;
+    HIPCHK(h, launch_wide((int)W.net.K, dim3((uint32_t)blocks), W.space.shmem, h->stream, P));
+    return BSX_OK;
+}
+
+// The same over samples [first_sample, first_sample + count) of the seed behind k0 (attract; bsx_sample.h)
+int wide_enqueue_sampled(bsx_handle h, WideHost& W, WideParams& P, uint64_t k0, uint64_t first_sample, uint64_t count, uint64_t max_t) {
+    uint64_t blocks = 0;
+    if (int rc = wide_fill_launch(h, W, P, count, max_t, &blocks)) return rc;
+    P.sample_k0 = k0;
+    P.sample_first = first_sample;
+    P.sample_variants = W.space.variant_count;
+    HIPCHK(h, launch_wide_sampled((int)W.net.K, dim3((uint32_t)blocks), W.space.shmem, h->stream, P));
     return BSX_OK;
 }
 
 // One launch, waited for: its counters and its device time.
-int wide_launch(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t, unsigned long long (&ctr)[4],
-                float& ms) {
-    HIPCHK(h, hipMemsetAsync(h->wide->d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
+int wide_launch(bsx_handle h, WideHost& W, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t,
+                unsigned long long (&ctr)[4], float& ms) {
+    HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    if (int rc = wide_enqueue(h, P, first, count, max_t)) return rc;
-    return wide_timed_wait(h, ctr, ms);
+    if (int rc = wide_enqueue(h, W, P, first, count, max_t)) return rc;
+    return wide_timed_wait(h, W, ctr, ms);
 }
 
 static int wide_sim(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* offsets,
@@ -104,10 +147,11 @@ static int wide_sim(bsx_handle h, const bsx_index* first, uint64_t count, uint64
                     uint64_t* final_states, uint64_t* digests, bsx_stats* stats) {
     const double t_begin = now_ms();
     if (stats) std::memset(stats, 0, sizeof(*stats));
+    WideHost& W = *h->wide;
     if (count == 0) return BSX_OK;
     if (max_t >= kStepLimit) return fail(h, BSX_ERR_UNSUPPORTED, "simulation length above the engine's step limit");
     HIPCHK(h, hipSetDevice(h->device));
-    const uint32_t w64 = h->wide->net.w64;
+    const uint32_t w64 = W.net.w64;
     DevBuf<uint64_t> d_traj, d_final, d_dig, d_off, d_tlen, d_ooff;
     WideParams P{};
     P.mode = kWideSimulate;
@@ -121,7 +165,7 @@ static int wide_sim(bsx_handle h, const bsx_index* first, uint64_t count, uint64
     }
     unsigned long long ctr[4];
     float ms = 0.f;
-    if (int rc = wide_launch(h, P, first, count, max_t, ctr, ms)) return rc;
+    if (int rc = wide_launch(h, W, P, first, count, max_t, ctr, ms)) return rc;
     if (trajectories) HIPCHK(h, hipMemcpy(trajectories, d_traj.p, traj_words * 8, hipMemcpyDeviceToHost));
     if (final_states) HIPCHK(h, hipMemcpy(final_states, d_final.p, count * w64 * 8, hipMemcpyDeviceToHost));
     if (digests) HIPCHK(h, hipMemcpy(digests, d_dig.p, count * 8, hipMemcpyDeviceToHost));
@@ -199,7 +243,7 @@ int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, co
         Q.state_offsets = want_states ? d_off.p + at : nullptr;
         Q.on_counts = count_on ? d_on.p + at * n_nodes : nullptr;
         Q.closed = want_closed ? d_closed.p + at : nullptr;
-        HIPCHK(h, launch_wide_profile((int)W.net.K, dim3((uint32_t)wide_blocks(h, m, shmem)), shmem, h->stream, Q));
+        HIPCHK(h, launch_wide_profile((int)W.net.K, dim3((uint32_t)wide_blocks(h, W, m, shmem)), shmem, h->stream, Q));
     }
     if (keep_states) {
         keep_states->launches = launches;
@@ -207,7 +251,7 @@ int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, co
     }
     unsigned long long ctr[4] = {0, 0, 0, 0};
     float ms = 0.f;
-    if (int rc = wide_timed_wait(h, ctr, ms)) return rc;
+    if (int rc = wide_timed_wait(h, W, ctr, ms)) return rc;
     if (on_counts) HIPCHK(h, hipMemcpy(on_counts, d_on.p, n * n_nodes * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (states && state_words) HIPCHK(h, hipMemcpy(states, d_states.p, state_words * 8, hipMemcpyDeviceToHost));
     if (closed) HIPCHK(h, hipMemcpy(closed, d_closed.p, n, hipMemcpyDeviceToHost));
@@ -223,16 +267,17 @@ static int wide_target_times(bsx_handle h, const bsx_index* first, uint64_t coun
     t_hit.assign(count, kWideNone);
     if (count == 0) return BSX_OK;
     HIPCHK(h, hipSetDevice(h->device));
+    WideHost& W = *h->wide;
     WideParams P{};
     P.mode = kWideTarget;
-    wide_target_words(h->wide->net.n, mask_words, code_words, P.tmask, P.tcode);
+    wide_target_words(W.net.n, mask_words, code_words, P.tmask, P.tcode);
     DevBuf<uint32_t> d_thit;
     HIPCHK(h, d_thit.alloc(count));
     HIPCHK(h, hipMemset(d_thit.p, 0xFF, count * 4));
     P.t_hit = d_thit.p;
     unsigned long long ctr[4];
     float ms = 0.f;
-    if (int rc = wide_launch(h, P, first, count, max_t, ctr, ms)) return rc;
+    if (int rc = wide_launch(h, W, P, first, count, max_t, ctr, ms)) return rc;
     HIPCHK(h, hipMemcpy(t_hit.data(), d_thit.p, count * 4, hipMemcpyDeviceToHost));
     put_stats(stats, count, ctr[0], ctr[1], ms, 1, t_begin);
     if (ctr[2]) return fail(h, BSX_ERR_STEP_LIMIT, "a trajectory reached the internal step limit");
@@ -290,7 +335,7 @@ int wide_run_target_summary(bsx_handle h, const bsx_index* first, uint64_t count
     WideParams P0{};
     P0.mode = kWideTarget;
     wide_target_words(W.net.n, mask_words, code_words, P0.tmask, P0.tcode);
-    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(h, 1ull << 24));
+    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(h, W, 1ull << 24));
     const uint32_t bins_alloc = std::max<uint32_t>(hist_bins, 1);
     HIPCHK(h, W.d_thit.reserve(chunk));
     HIPCHK(h, W.d_hist.reserve(bins_alloc));
@@ -320,7 +365,7 @@ int wide_run_target_summary(bsx_handle h, const bsx_index* first, uint64_t count
         if (!timing) { HIPCHK(h, hipEventRecord(h->ev0, h->stream)); timing = true; }
         WideParams P = P0;
         P.t_hit = W.d_thit.p;
-        if (int rc = wide_enqueue(h, P, &at, m, max_t)) return rc;
+        if (int rc = wide_enqueue(h, W, P, &at, m, max_t)) return rc;
         HIPCHK(h, launch_wide_reduce_target(W.d_thit.p, m, W.d_hist.p, hist_bins, W.d_out.p, h->stream));
         launches += 2;
         if (listed < cap) {                     // the list still has room: this chunk's hit times, in index order

@@ -1,6 +1,7 @@
 // bsx_run_attract_wide: attract over the wide-state family's per-problem records, aggregated by key -- on the device
 // (bsx_wide_reduce.hip) or, with BSX_WIDE_HOST_REDUCE=1 or a table beyond kWideReduceMaxCap, chunk by chunk on the host
-// (the path before bsx_wide_reduce.hip; kept for A/B runs and tests).
+// (the path before bsx_wide_reduce.hip; kept for A/B runs and tests).  Both legs take the source of their launches as
+// an argument (WideAttractSource, bsx_wide_host.h): bsx_run_attract_sampled (bsx_sample_api.cpp) runs them over samples.
 #include <algorithm>
 #include <array>
 #include <cstring>
@@ -44,10 +45,9 @@ static WideParams attract_params(uint32_t* d_info, uint64_t* d_keys, uint64_t ma
 // kInlineRecs records come back with the header in that one copy; a table with more costs a second copy.
 static constexpr uint32_t kInlineRecs = 256;
 
-static int attract_wide_device(bsx_handle h, const bsx_index& first, uint64_t count, uint64_t chunk, uint64_t max_t,
-                               uint64_t max_len, bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out,
-                               bsx_u128* n_no_attractor, bsx_stats2* stats, double t_begin) {
-    WideHost& W = *h->wide;
+int bsx::attract_wide_device(bsx_handle h, WideHost& W, WideAttractSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
+                             bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor, bsx_stats2* stats,
+                             double t_begin) {
     const uint32_t w64 = W.net.w64;
     // a range of `count` problems has at most `count` attractors: the device structures follow the smaller of the two,
     // so a caller's very large cap ("no limit") costs nothing
@@ -68,9 +68,8 @@ static int attract_wide_device(bsx_handle h, const bsx_index& first, uint64_t co
     uint32_t wide_launches = 0;
     for (uint64_t done = 0; done < count; done += chunk, ++wide_launches) {
         const uint64_t m = std::min(chunk, count - done);
-        const bsx_index at = index_plus(first, done, h->sp.n_any);
         WideParams P = attract_params(W.d_info.p, W.d_keys.p, max_len);
-        if (int rc = wide_enqueue(h, P, &at, m, max_t)) return rc;
+        if (int rc = src.enqueue(P, done, m)) return rc;
         HIPCHK(h, launch_wide_reduce_attract(W.d_info.p, W.d_keys.p, m, w64, W.d_table.p, slots, d_hdr, h->stream));
     }
     HIPCHK(h, launch_wide_reduce_drain(W.d_table.p, slots, d_recs, dcap, d_hdr, W.d_ctr.p, h->stream));
@@ -107,10 +106,10 @@ static int attract_wide_device(bsx_handle h, const bsx_index& first, uint64_t co
 }
 
 // Host path: every chunk's records come back and are aggregated here by key; one launch and one wait per chunk.
-static int attract_wide_host(bsx_handle h, const bsx_index& first, uint64_t count, uint64_t chunk, uint64_t max_t,
-                             uint64_t max_len, bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out,
-                             bsx_u128* n_no_attractor, bsx_stats2* stats, double t_begin) {
-    const uint32_t w64 = h->wide->net.w64;
+int bsx::attract_wide_host(bsx_handle h, WideHost& W, WideAttractSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
+                           bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor, bsx_stats2* stats,
+                           double t_begin) {
+    const uint32_t w64 = W.net.w64;
     DevBuf<uint32_t> d_info;
     DevBuf<uint64_t> d_keys;
     HIPCHK(h, d_info.alloc(chunk * 4));
@@ -126,11 +125,13 @@ static int attract_wide_host(bsx_handle h, const bsx_index& first, uint64_t coun
     bool limit = false;
     for (uint64_t done = 0; done < count; done += chunk) {
         const uint64_t m = std::min(chunk, count - done);
-        const bsx_index at = index_plus(first, done, h->sp.n_any);
         WideParams P = attract_params(d_info.p, d_keys.p, max_len);
         unsigned long long ctr[4];
         float ms = 0.f;
-        if (int rc = wide_launch(h, P, &at, m, max_t, ctr, ms)) return rc;
+        HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));     // (one launch, waited for: wide_launch)
+        HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+        if (int rc = src.enqueue(P, done, m)) return rc;
+        if (int rc = wide_timed_wait(h, W, ctr, ms)) return rc;
         HIPCHK(h, hipMemcpy(info.data(), d_info.p, m * 16, hipMemcpyDeviceToHost));
         HIPCHK(h, hipMemcpy(keys.data(), d_keys.p, m * w64 * 8, hipMemcpyDeviceToHost));
         kms += ms; ++launches; exec += ctr[1]; ref_steps += ctr[0];
@@ -191,15 +192,25 @@ extern "C" int bsx_run_attract_wide(bsx_handle h, bsx_u128 first_flat, bsx_u128 
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (count_flat.hi) return fail(h, BSX_ERR_UNSUPPORTED, "wide networks: at most 2^64 - 1 problems per call");
     const uint64_t count = count_flat.lo;
+    WideHost& W = *h->wide;
+    if (int rc = wide_check_enumerable(h, W)) return rc;
     bsx_index first{};
     if (const LowerStatus s = wide_split_flat(first_flat, h->sp.n_any, first)) return fail(h, s.status, s.msg);
     if (int rc = check_range(h, &first, count)) return rc;
     if (int rc = check_max_t(h, max_t)) return rc;
     if (count == 0) return BSX_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(h, 1ull << 18));
+    const uint64_t chunk = std::min<uint64_t>(count, wide_chunk(h, W, 1ull << 18));
     // (more than kWideReduceMaxCap possible attractors: the device table would take gigabytes; such a call is reduced
     // on the host, which allocates per attractor found)
     const bool on_device = !h->knobs.wide_host_reduce && std::min<uint64_t>(cap, count) <= kWideReduceMaxCap;
-    return (on_device ? attract_wide_device : attract_wide_host)(h, first, count, chunk, max_t, max_len, table, cap, n_out, n_no_attractor, stats, t_begin);
+    struct Range : WideAttractSource {      // consecutive problem indices from `first`
+        bsx_handle h; WideHost& W; const bsx_index& first; uint64_t max_t;
+        Range(bsx_handle h_, WideHost& W_, const bsx_index& f, uint64_t t) : h(h_), W(W_), first(f), max_t(t) {}
+        int enqueue(WideParams& P, uint64_t done, uint64_t m) override {
+            const bsx_index at = index_plus(first, done, h->sp.n_any);
+            return wide_enqueue(h, W, P, &at, m, max_t);
+        }
+    } src(h, W, first, max_t);
+    return (on_device ? attract_wide_device : attract_wide_host)(h, W, src, count, chunk, max_len, table, cap, n_out, n_no_attractor, stats, t_begin);
 }

@@ -10,6 +10,8 @@
 namespace bsx {
 
 hipError_t launch_wide(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& P);
+hipError_t launch_wide_sampled(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& P);
+hipError_t launch_sample_problems(const WideSampleListParams& Q, hipStream_t st);
 hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, const WideProfileParams& Q);
 hipError_t launch_wide_trans(int k, dim3 grid, size_t shmem, hipStream_t st, const WideTransParams& Q);
 hipError_t launch_wide_trans_build(const WideTransParams& Q, hipStream_t st);
@@ -44,15 +46,16 @@ inline void wide_fill_net(const WideHost& W, WideParams& P) {
 }
 
 // Workgroups of a launch over `count` trajectories with `shmem` bytes of LDS each.
-inline uint64_t wide_blocks(const bsx_engine* h, uint64_t count, size_t shmem) {
-    return wide_grid_blocks(count, h->wide->space.L, shmem, (uint32_t)h->prop.multiProcessorCount);
+inline uint64_t wide_blocks(const bsx_engine* h, const WideHost& W, uint64_t count, size_t shmem) {
+    return wide_grid_blocks(count, W.space.L, shmem, (uint32_t)h->prop.multiProcessorCount);
 }
 
 // The end of a timed run of launches (the caller has zeroed d_ctr and recorded ev0 in front of it): records ev1, brings the
 // four counters back (and `bytes` of a caller's own counter block with them), waits, reads the device time.
-inline int wide_timed_wait(bsx_handle h, unsigned long long (&ctr)[4], float& ms, void* also = nullptr, const void* d_also = nullptr, size_t bytes = 0) {
+inline int wide_timed_wait(bsx_handle h, WideHost& W, unsigned long long (&ctr)[4], float& ms, void* also = nullptr, const void* d_also = nullptr,
+                           size_t bytes = 0) {
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    HIPCHK(h, hipMemcpyAsync(ctr, h->wide->d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ctr, W.d_ctr.p, sizeof(ctr), hipMemcpyDeviceToHost, h->stream));
     if (bytes) HIPCHK(h, hipMemcpyAsync(also, d_also, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -60,14 +63,44 @@ inline int wide_timed_wait(bsx_handle h, unsigned long long (&ctr)[4], float& ms
 }
 
 // Problems per k_wide launch of a chunked run: BSX_WIDE_CHUNK clamped to [32 * L, 2^18], else `dflt`.
-inline uint64_t wide_chunk(const bsx_engine* h, uint64_t dflt) {
+inline uint64_t wide_chunk(const bsx_engine* h, const WideHost& W, uint64_t dflt) {
     if (!h->knobs.wide_chunk_set) return dflt;
-    return std::max<uint64_t>(32ull * h->wide->space.L, std::min<uint64_t>(h->knobs.wide_chunk, 1ull << 18));
+    return std::max<uint64_t>(32ull * W.space.L, std::min<uint64_t>(h->knobs.wide_chunk, 1ull << 18));
 }
 
-// bsx_wide_api.cpp: one k_wide launch enqueued; one launch waited for
-int wide_enqueue(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t);
-int wide_launch(bsx_handle h, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t, unsigned long long (&ctr)[4],
-                float& ms);
+// The helpers below take the WideHost they work on: a wide handle's own (h->wide), or the second lowering that the sampled
+// calls keep on a handle of the <= BSX_MAX_NODES family (h->sample_wide, bsx_sample_api.cpp).
+
+// bsx_wide_api.cpp: a network / a problem space lowered into W and uploaded (the arrays have passed the callers' checks)
+int wide_upload_network(bsx_handle h, WideHost& W, uint32_t n_nodes, const uint32_t* pred_offsets, const uint32_t* pred_idx,
+                        const uint32_t* tt_word_offsets, const uint64_t* tt_words);
+int wide_upload_space(bsx_handle h, WideHost& W, const uint64_t* origin_state_words, const uint32_t* any_nodes, uint32_t n_any,
+                      const bsx_fixed* fixed, uint32_t n_fixed, const bsx_fixed_var* fixed_var, uint32_t n_fixed_var,
+                      const bsx_pert* sched, uint32_t n_sched, const bsx_pert_var* pert_var, uint32_t n_pert_var);
+// bsx_wide_api.cpp: one k_wide launch enqueued; one launch waited for; one k_wide_sampled launch enqueued
+int wide_enqueue(bsx_handle h, WideHost& W, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t);
+int wide_launch(bsx_handle h, WideHost& W, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t,
+                unsigned long long (&ctr)[4], float& ms);
+int wide_enqueue_sampled(bsx_handle h, WideHost& W, WideParams& P, uint64_t k0, uint64_t first_sample, uint64_t count, uint64_t max_t);
+// An enumerating call on a space with more 'any' nodes than a bsx_index holds (only the sampled calls reach such a space).
+// The calls that take a bsx_index are refused by check_range (bsx_host.h); this is the same refusal for the flat index
+// of bsx_run_attract_wide, in front of its split.
+inline int wide_check_enumerable(bsx_handle h, const WideHost& W) {
+    if (W.space.n_any > 64 * BSX_MAX_WORDS)
+        return fail(h, BSX_ERR_UNSUPPORTED, "more 'any' nodes than a bsx_index holds (64 * BSX_MAX_WORDS)");
+    return BSX_OK;
+}
+
+// bsx_wide_attract_api.cpp: the two legs of an attract call over `count` problems in launches of `chunk`, behind
+// bsx_run_attract_wide and bsx_run_attract_sampled.  The source enqueues the launch over problems [done, done + m) of the
+// call (consecutive indices, or samples of a seed); everything behind the launch is the same for both.
+struct WideAttractSource {
+    virtual int enqueue(WideParams& P, uint64_t done, uint64_t m) = 0;
+    virtual ~WideAttractSource() = default;
+};
+int attract_wide_device(bsx_handle h, WideHost& W, WideAttractSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
+                        bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor, bsx_stats2* stats, double t_begin);
+int attract_wide_host(bsx_handle h, WideHost& W, WideAttractSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
+                      bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor, bsx_stats2* stats, double t_begin);
 
 }  // namespace bsx

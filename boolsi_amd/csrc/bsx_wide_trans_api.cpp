@@ -66,8 +66,8 @@ extern "C" int bsx_run_attractor_transitions_wide(bsx_handle h, const uint64_t* 
     while (edge_slots < 2 * (out_cap + 1)) edge_slots <<= 1;           // (+ 1: one edge too many must still find a slot)
     const uint64_t flip_chunk = h->knobs.wtrans_chunk ? std::min<uint64_t>(h->knobs.wtrans_chunk, 1ull << 28) : kWideTransFlipChunk;
     // the x_0 spill takes rows * L words per workgroup
-    const uint64_t most_blocks = std::max(wide_blocks(h, std::min(n, kWideTransRowChunk), shmem),
-                                          wide_blocks(h, std::min(std::max<uint64_t>(flips, 1), flip_chunk), shmem));
+    const uint64_t most_blocks = std::max(wide_blocks(h, W, std::min(n, kWideTransRowChunk), shmem),
+                                          wide_blocks(h, W, std::min(std::max<uint64_t>(flips, 1), flip_chunk), shmem));
 
     DevBuf<uint64_t> d_row_first, d_row_keys;
     DevBuf<uint32_t> d_owners, d_row_info, d_free, d_exits, d_x0;
@@ -113,7 +113,7 @@ extern "C" int bsx_run_attractor_transitions_wide(bsx_handle h, const uint64_t* 
     for (uint64_t at = 0; at < n; at += kWideTransRowChunk, ++launches) {
         Q.first = at;
         Q.count = std::min<uint64_t>(kWideTransRowChunk, n - at);
-        HIPCHK(h, launch_wide_trans((int)W.net.K, dim3((uint32_t)wide_blocks(h, Q.count, shmem)), shmem, h->stream, Q));
+        HIPCHK(h, launch_wide_trans((int)W.net.K, dim3((uint32_t)wide_blocks(h, W, Q.count, shmem)), shmem, h->stream, Q));
     }
     HIPCHK(h, launch_wide_trans_build(Q, h->stream));
     ++launches;
@@ -121,14 +121,14 @@ extern "C" int bsx_run_attractor_transitions_wide(bsx_handle h, const uint64_t* 
     for (uint64_t at = 0; at < flips; at += flip_chunk, ++launches) {
         Q.first = at;
         Q.count = std::min<uint64_t>(flip_chunk, flips - at);
-        HIPCHK(h, launch_wide_trans((int)W.net.K, dim3((uint32_t)wide_blocks(h, Q.count, shmem)), shmem, h->stream, Q));
+        HIPCHK(h, launch_wide_trans((int)W.net.K, dim3((uint32_t)wide_blocks(h, W, Q.count, shmem)), shmem, h->stream, Q));
     }
     HIPCHK(h, launch_trans_drain(d_edges.p, edge_slots, d_out.p, out_cap, d_tc.p, h->stream));
     ++launches;
     // the call's one wait (ev0: wide_run_profile, in front of its first launch)
     unsigned long long ctr[4] = {0, 0, 0, 0};
     float ms = 0.f;
-    if (int rc = wide_timed_wait(h, ctr, ms, &tc, d_tc.p, sizeof(tc))) return rc;
+    if (int rc = wide_timed_wait(h, W, ctr, ms, &tc, d_tc.p, sizeof(tc))) return rc;
 
     if (tc.open_row != kTransNoRow)
         return fail(h, BSX_ERR_INVALID, who + ": row " + std::to_string(tc.open_row) + " is not closed: its key does not return after its length");

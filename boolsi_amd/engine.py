@@ -355,6 +355,26 @@ class Engine:
                                                    C.byref(st)))
         return AttractResult(table[:n_out.value].copy(), int(none), None, st.as_dict())
 
+    def attract_sampled(self, seed, first, count, max_t=inf, max_len=inf, cap=65536):
+        """bsx_run_attract_sampled: attract over samples [first, first + count) of `seed` (include/bsx.h defines sample
+        j) -> AttractResult with a _lib.ATTR_REC2W table; count of a record = samples that reached it."""
+        table = getattr(self, '_attr_table2w', None)
+        if table is None or len(table) < cap:
+            table = self._attr_table2w = np.zeros(cap, _lib.ATTR_REC2W)
+        n_out, none, st = C.c_uint32(), C.c_uint64(), _lib.Stats2()
+        self._check(self._lib.bsx_run_attract_sampled(self._h, int(seed), int(first), int(count), _cap(max_t), _cap(max_len),
+                                                      ptr(table), cap, C.byref(n_out), C.byref(none), C.byref(st)))
+        return AttractResult(table[:n_out.value].copy(), none.value, None, st.as_dict())
+
+    def sample_problems(self, seed, samples):
+        """bsx_sample_problems: the problems behind the listed sample numbers of `seed`
+        -> (states (n, W) uint64: s(0) of each sample, variants (n,) uint64: its variant number)."""
+        samples = np.ascontiguousarray(samples, np.uint64)
+        states = np.zeros((len(samples), self.net.n_words), np.uint64)
+        variants = np.zeros(len(samples), np.uint64)
+        self._check(self._lib.bsx_sample_problems(self._h, int(seed), ptr(samples), len(samples), ptr(states), ptr(variants)))
+        return states, variants
+
     def target(self, first, count, max_t, mask_words, code_words, cap=None):
         cap = count if cap is None else cap
         hits = np.zeros(max(cap, 1), _lib.HIT)

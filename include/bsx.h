@@ -36,7 +36,8 @@ extern "C" {
 #define BSX_T_INF            UINT64_MAX   /* "no cap" for max_t / max_len (the CLI's inf) */
 /* Networks of BSX_MAX_NODES < n <= BSX_MAX_NODES_WIDE nodes run on the wide-state family (DESIGN.md "Wide networks"):
  * simulate, trajectories, target and target summary through the entry points below, attract through
- * bsx_run_attract_wide only.  Their 'any' nodes must fit a bsx_index (at most 64 * BSX_MAX_WORDS). */
+ * bsx_run_attract_wide only.  Their 'any' nodes must fit a bsx_index (at most 64 * BSX_MAX_WORDS) for every call that
+ * enumerates; bsx_run_attract_sampled takes spaces with up to n 'any' nodes. */
 #define BSX_MAX_NODES_WIDE   1024
 #define BSX_MAX_STATE_WORDS  16     /* uint64 words per state / key of the wide family */
 #define BSX_LUT_WIDE         3      /* bsx_network_info's lut_mode for a network lowered to the wide family */
@@ -230,6 +231,41 @@ int  bsx_run_attract_wide(bsx_handle h, bsx_u128 first, bsx_u128 count,
                           uint64_t max_t, uint64_t max_len,
                           bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out,
                           bsx_u128* n_no_attractor, bsx_stats2* stats);
+
+/* ---- attract over sampled initial conditions (no reference analogue: the reference enumerates) -------------------------
+ * For spaces too large to enumerate.  Sample j of seed `seed` is a problem of the current space; this definition is
+ * NORMATIVE, part of the ABI, and implemented in boolsi_amd/csrc/bsx_sample.h.  All arithmetic is mod 2^64.
+ *
+ *     G      = 0x9E3779B97F4A7C15
+ *     mix(z) : z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *     k0     = mix(seed + G)
+ *     kb(b)  = mix(k0 + G * (b + 1))                     b = j >> 6   (a block of 64 samples)
+ *     A(b,a) = mix(kb(b) + G * (a + 1))                  a = 0 .. n_any-1, the order of any_nodes
+ *     U(j)   = mix(kb(j >> 6) + G * (n_any + 1 + (j & 63)))
+ *
+ *   - the a-th 'any' node of sample j has the state bit (j & 63) of A(j >> 6, a);
+ *   - its variant number is (U(j) * V) >> 64, V the space's variant count: one 64 x 64 -> high multiply, whose bias is
+ *     below V / 2^64 (a variant is drawn for floor or ceil of 2^64 / V values of U);
+ *   - equivalently it is the flat index I(j) = sum of bit_a * 2^a + variant * 2^n_any of batching.py:212-229.
+ * Hence a sampled call over [first, first + n) is a pure function of (seed, first, n), and disjoint sample ranges add up
+ * to the call over their union (the multi-GPU partition rests on that).  Nothing here is an enumeration: the first n
+ * samples of a seed are n independent draws, the first n indices of a space vary its low digits only.
+ *
+ * On the wide family a space may have up to n 'any' nodes.  With more than a bsx_index holds (64 * BSX_MAX_WORDS) only the
+ * two calls below (and profile, correlations, transitions, which do not read the 'any' nodes) work on it; every entry
+ * point that takes a bsx_index or a flat index returns BSX_ERR_UNSUPPORTED.  A space whose variant count does not fit
+ * 64 bits is BSX_ERR_UNSUPPORTED here as everywhere. */
+
+/* attract over samples [first_sample, first_sample + n_samples) of seed `seed` (definition above): bsx_run_attract_wide's
+ * records, sums, order, capacity rules and statistics; count of a record = samples that reached it.  Works on handles of
+ * both families with the same results (a handle of the <= BSX_MAX_NODES family lowers its network and space a second
+ * time, on the first sampled call).  BSX_ERR_INVALID if first_sample + n_samples wraps. */
+int  bsx_run_attract_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample, uint64_t n_samples,
+                             uint64_t max_t, uint64_t max_len, bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out,
+                             uint64_t* n_no_attractor, bsx_stats2* stats);
+/* the problems behind listed sample numbers: states[q * W + w] = s(0) of sample samples[q], variants[q] (nullable) */
+int  bsx_sample_problems(bsx_handle h, uint64_t seed, const uint64_t* samples, uint64_t n,
+                         uint64_t* states, uint64_t* variants);
 
 /* target (target.py:109-133): hits in ascending offset order into hits[0..*n_hits); mask/code are W words
  * (target node set / target substate code, input.py:580-661). */
