@@ -1,7 +1,7 @@
 // bsx_run_node_correlations (include/bsx.h): the matrix S behind the frequency-weighted Spearman correlations of a
-// whole attractor table.  The profile kernels leave the on-counts in HBM (profile_lanes / wide_run_profile with
-// keep_on); the kernels of bsx_corr.hip turn them into ranks and S.  Everything is checked before anything is
-// launched; the handle's problem space, cycle journal and mirror image are not touched.
+// whole attractor table.  The profile stage (bsx_table_host.h) leaves the on-counts in HBM, wanted on the device
+// whether or not the caller takes them; the kernels of bsx_corr.hip turn them into ranks and S.  Everything is
+// checked before anything is launched; the handle's problem space, cycle journal and mirror image are not touched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,9 +9,8 @@
 #include <vector>
 
 #include "bsx_corr.h"
-#include "bsx_engine.h"
-#include "bsx_host.h"
 #include "bsx_ranks.h"
+#include "bsx_table_host.h"
 
 using namespace bsx;
 
@@ -27,9 +26,9 @@ extern "C" int bsx_run_node_correlations(bsx_handle h, const uint64_t* keys, uin
     const double t_begin = now_ms();
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n == 0) return BSX_OK;
-    const char* who = "bsx_run_node_correlations";
-    uint64_t sum_len = 0, state_words = 0;
-    if (int rc = profile_check_args(h, who, keys, key_stride, lengths, n, nullptr, nullptr, &sum_len, &state_words)) return rc;
+    const TableView table{keys, key_stride, lengths, n};
+    TableSizes sizes;
+    if (int rc = table_check_args(h, "bsx_run_node_correlations", table, false, nullptr, sizes)) return rc;
     if (!frequencies || !s_matrix) return fail(h, BSX_ERR_INVALID, "bsx_run_node_correlations: frequencies or s_matrix is null");
     uint64_t total = 0;
     switch (corr_total(&frequencies[0].lo, n, &total)) {
@@ -43,13 +42,15 @@ extern "C" int bsx_run_node_correlations(bsx_handle h, const uint64_t* keys, uin
         return fail(h, BSX_ERR_UNSUPPORTED, "bsx_run_node_correlations: more than 2^31 cells (attractors x nodes)");
     HIPCHK(h, hipSetDevice(h->device));
 
-    // the profile: on-counts stay in d_on; it waits for the device once and fills `pst`
-    DevBuf<uint32_t> d_on;
+    // the profile: on-counts stay on the device; its collect waits for the device once and fills `pst`
+    const ProfileOut out{on_counts, nullptr, closed};
+    ProfileWant want = profile_want(out);
+    want.on_counts = true;
+    ProfileDev prof;
     bsx_stats pst{};
-    const int rc = h->wide ? wide_run_profile(h, keys, key_stride, lengths, n, on_counts, nullptr, nullptr, 0, closed, sum_len, &pst, &d_on)
-                           : profile_lanes(h, keys, key_stride, lengths, n, on_counts, nullptr, nullptr, 0, closed, sum_len, &pst,
-                                           t_begin, &d_on, nullptr);
-    if (rc) return rc;
+    if (int rc = profile_stage(h, table, want, nullptr, 0, prof)) return rc;
+    if (int rc = profile_enqueue(h, table, prof)) return rc;
+    if (int rc = profile_collect(h, table, prof, out, sizes.sum_len, &pst, t_begin)) return rc;
 
     // columns per batch: the sort's and the ranks' working set is 32 bytes per cell of a batch plus rocprim's own
     const uint64_t batch_cells = h->knobs.corr_batch_cells ? std::min<uint64_t>(h->knobs.corr_batch_cells, BSX_CORR_MAX_CELLS)
@@ -79,7 +80,7 @@ extern "C" int bsx_run_node_correlations(bsx_handle h, const uint64_t* keys, uin
     HIPCHK(h, d_s.alloc((uint64_t)n_nodes * n_nodes));
 
     CorrBatch B{};
-    B.on_counts = d_on.p; B.lengths = d_len.p; B.freq = d_freq.p;
+    B.on_counts = prof.on_counts.p; B.lengths = d_len.p; B.freq = d_freq.p;
     B.n = n; B.n_nodes = n_nodes; B.total = total;
     B.keys = d_keys.p; B.keys_sorted = d_keys_sorted.p; B.vals = d_vals.p; B.vals_sorted = d_vals_sorted.p;
     B.p_incl = d_pincl.p; B.d = d_d.p; B.ranks = ranks ? d_ranks.p : nullptr;

@@ -1,6 +1,7 @@
 // Host-side internals shared by the translation units behind include/bsx.h (bsx_api.cpp, bsx_target_api.cpp,
 // bsx_simulate_api.cpp, bsx_attract_api.cpp, bsx_cascade.cpp, bsx_fgraph_api.cpp, bsx_wide_api.cpp, bsx_wide_attract_api.cpp, bsx_wide_trans_api.cpp,
-// bsx_sample_api.cpp, bsx_comm.cpp): the engine handle, device buffers, error plumbing.  Not part of the ABI.
+// bsx_sample_api.cpp, bsx_comm.cpp, and behind bsx_table_host.h the attractor-table calls): the engine handle, device
+// buffers, error plumbing.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,13 +41,6 @@ struct DevBuf {
         if (e != hipSuccess || v.empty()) return e;
         return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
     }
-};
-
-// what profile_lanes leaves on the device for a caller that goes on enqueueing behind it (keep_states)
-struct ProfileKeep {
-    DevBuf<uint64_t> keys, lengths, offsets, states;
-    DevBuf<uint8_t> closed;
-    uint32_t launches = 0;
 };
 
 // host copies of the arguments of bsx_set_network / bsx_set_problem_space (HostModel holds only the first table word)
@@ -195,18 +189,6 @@ int wide_run_target(bsx_handle h, const bsx_index* first, uint64_t count, uint64
 int wide_run_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
                             const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
                             uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats, double t_call);
-int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
-                     uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
-                     uint64_t sum_len, bsx_stats* stats, DevBuf<uint32_t>* keep_on, ProfileKeep* keep_states = nullptr);
-// bsx_profile_api.cpp: the checks and the per-lane family of bsx_run_attractor_profile, shared with
-// bsx_run_node_correlations (bsx_corr_api.cpp), which keeps the on-counts on the device (keep_on), and with
-// bsx_run_attractor_transitions (bsx_trans_api.cpp), which keeps the states there (keep_states)
-int profile_check_args(bsx_handle h, const char* who, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths,
-                       uint64_t n, const uint64_t* states, const uint64_t* state_offsets, uint64_t* sum_len_out,
-                       uint64_t* state_words_out);
-int profile_lanes(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
-                  uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
-                  uint64_t sum_len, bsx_stats* stats, double t_begin, DevBuf<uint32_t>* keep_on, ProfileKeep* keep_states);
 }  // namespace bsx
 
 static inline int fail(bsx_handle h, int status, const std::string& msg) {

@@ -1,4 +1,4 @@
-// What a lowering unit (bsx_lane_lower.h, bsx_wide_lower.h) answers when it refuses its input.  No HIP here.
+// What a lowering unit (bsx_lane_lower.h, bsx_wide_lower.h, bsx_table_lower.h) answers when it refuses its input.  No HIP here.
 #pragma once
 #include "bsx.h"
 

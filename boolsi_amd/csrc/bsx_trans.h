@@ -1,19 +1,16 @@
 // Single-node flip transitions of an attractor table (bsx_run_attractor_transitions, include/bsx.h): structures
-// shared by bsx_trans_api.cpp and the kernels (bsx_trans.hip, bsx_trans_kernel.h), and the launch prototypes.
+// shared by bsx_trans_api.cpp and the kernels (bsx_trans.hip, bsx_trans_kernel.h), and the launch prototypes.  The
+// records without HIP (TransEdge, TransCtr, the limits) are in bsx_trans_records.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "bsx_device.h"
+#include "bsx_trans_records.h"
 
 namespace bsx {
 
-constexpr uint64_t kTransMaxStates = 1ull << 28;    // BSX_TRANS_MAX_STATES
-constexpr uint64_t kTransFlipChunk = 1ull << 28;    // flips per launch of the walk kernel
 constexpr uint32_t kTransLdsEdges = 256;            // entries of a workgroup's LDS edge table (power of two)
 constexpr uint32_t kTransLdsProbes = 4;             // ... probes before a record goes to the HBM table directly
-constexpr uint32_t kTransOutside = 0xFFFFFFFEu;     // BSX_TRANS_OUTSIDE
-constexpr uint32_t kTransUnresolved = 0xFFFFFFFFu;  // BSX_TRANS_UNRESOLVED
-constexpr uint32_t kTransNoRow = 0xFFFFFFFFu;
 
 // One slot of the edge tables (LDS and HBM).  key = ((src << 32) | dst) + 1, 0 = free: src <= 2^32 - 4, so the sum
 // does not wrap.  The key is one word: whoever sees it sees all of it; count and sum_mu only ever take atomic adds.
@@ -23,23 +20,6 @@ struct TransEdgeSlot {
     unsigned long long sum_mu;
 };
 static_assert(sizeof(TransEdgeSlot) == 24, "edge slot layout");
-
-struct TransEdge {          // bsx_trans_edge
-    uint32_t src, dst;
-    uint64_t count, sum_mu;
-};
-static_assert(sizeof(TransEdge) == 24, "edge record layout");
-
-struct alignas(8) TransCtr {            // zeroed (open_row / dup_row: all ones) before the build
-    unsigned int open_row;              // least row whose walk did not close (kTransNoRow: none)
-    unsigned int dup_row;               // least of the later rows of two equal states (kTransNoRow: none)
-    unsigned int probe_full;            // k_trans_build: a probe went round the whole table (cannot happen at load <= 1/2)
-    unsigned int step_limit_hits;       // walks undecided at the step limit
-    unsigned int edge_overflow;         // the HBM edge table was full
-    unsigned int rows_undecided;        // wide family: closed rows whose own walk ran into the step limit (else unused)
-    unsigned long long n_edges;         // k_trans_drain's cursor
-    unsigned long long steps_exec;      // network updates of the walk kernel
-};
 
 // Cycle-state table in HBM: slot = owner, the index of a state in `states` plus one (0 = free), found by linear
 // probing from the state's hash.  n_slots is a power of two >= 2 * n_states, at least 2.

@@ -1,6 +1,7 @@
 // Host side of the wide-state family (bsx_wide.hip): upload of what bsx_wide_lower.cpp makes of a network of up to
 // BSX_MAX_NODES_WIDE nodes and its problem space, and the run entry points of include/bsx.h for such networks --
-// simulate, trajectories, target, profile.  (Attract: bsx_wide_attract_api.cpp; transitions: bsx_wide_trans_api.cpp.)
+// simulate, trajectories, target.  (Attract: bsx_wide_attract_api.cpp; profile: bsx_profile_api.cpp; transitions:
+// bsx_wide_trans_api.cpp.)
 // bsx_api.cpp hands a handle over here when its network has more than BSX_MAX_NODES nodes (or BSX_WIDE=1).
 #include <algorithm>
 #include <cstring>
@@ -187,76 +188,6 @@ int wide_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* 
         tmax = std::max(tmax, t_len[q]);
     }
     return wide_sim(h, first, n, tmax, offsets, t_len, out_offsets, words, out, nullptr, nullptr, stats);
-}
-
-// bsx_run_attractor_profile on the wide family (bsx_profile_api.cpp has checked every argument): one k_wide_profile
-// launch per BSX_PROFILE_CHUNK_WIDE attractors, all enqueued before the one wait.
-// keep_states (as profile_lanes): states and closure are written whether or not the caller wants them on the host and
-// every device buffer of the call stays in *keep_states; the launches are enqueued and NOT waited for, nothing is
-// copied back and `stats` is not written (the wide attractor transitions go on enqueueing behind them).
-int wide_run_profile(bsx_handle h, const uint64_t* keys, uint32_t key_stride, const uint64_t* lengths, uint64_t n,
-                     uint32_t* on_counts, uint64_t* states, const uint64_t* state_offsets, uint64_t state_words, uint8_t* closed,
-                     uint64_t sum_len, bsx_stats* stats, DevBuf<uint32_t>* keep_on, ProfileKeep* keep_states) {
-    static_assert(BSX_PROFILE_CHUNK_WIDE % (32 * 64) == 0, "a chunk is whole groups for every L");
-    const double t_begin = now_ms();
-    WideHost& W = *h->wide;
-    const uint32_t n_nodes = W.net.n;
-    WideProfileParams Q{};
-    wide_fill_net(W, Q.net);
-    if (Q.net.rows_ps > kWideProfileRows)                      // (before any device work, as every check of this call)
-        return fail(h, BSX_ERR_UNSUPPORTED, "wide profile: more rows per thread than the kernel holds");
-    ProfileKeep here;
-    ProfileKeep& kept = keep_states ? *keep_states : here;
-    DevBuf<uint64_t>&d_keys = kept.keys, &d_len = kept.lengths, &d_off = kept.offsets, &d_states = kept.states;
-    DevBuf<uint32_t> d_on_here;
-    DevBuf<uint32_t>& d_on = keep_on ? *keep_on : d_on_here;   // (keep_on: counted in any case, and left there)
-    const bool count_on = on_counts || keep_on;
-    DevBuf<uint8_t>& d_closed = kept.closed;
-    const bool want_states = states || keep_states, want_closed = closed || keep_states;
-    HIPCHK(h, d_keys.alloc(n * key_stride));
-    HIPCHK(h, hipMemcpy(d_keys.p, keys, n * key_stride * 8, hipMemcpyHostToDevice));
-    HIPCHK(h, d_len.alloc(n));
-    HIPCHK(h, hipMemcpy(d_len.p, lengths, n * 8, hipMemcpyHostToDevice));
-    if (want_states) {
-        HIPCHK(h, d_off.alloc(n));
-        HIPCHK(h, hipMemcpy(d_off.p, state_offsets, n * 8, hipMemcpyHostToDevice));
-        HIPCHK(h, d_states.alloc(state_words));
-    }
-    if (count_on) {
-        HIPCHK(h, d_on.alloc(n * n_nodes));
-        HIPCHK(h, hipMemsetAsync(d_on.p, 0, n * n_nodes * sizeof(uint32_t), h->stream));
-    }
-    if (want_closed) HIPCHK(h, d_closed.alloc(n));
-
-    Q.key_stride = key_stride;
-    Q.states = want_states ? d_states.p : nullptr;
-    Q.ctr = W.d_ctr.p;
-    const size_t shmem = (size_t)wide_profile_lds_words(W.net.rows, W.space.L, W.space.n_fslots) * 4;
-    uint32_t launches = 0;
-    HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-    for (uint64_t at = 0; at < n; at += BSX_PROFILE_CHUNK_WIDE, ++launches) {
-        const uint64_t m = std::min<uint64_t>(BSX_PROFILE_CHUNK_WIDE, n - at);
-        Q.count = m;
-        Q.keys = d_keys.p + at * key_stride;
-        Q.lengths = d_len.p + at;
-        Q.state_offsets = want_states ? d_off.p + at : nullptr;
-        Q.on_counts = count_on ? d_on.p + at * n_nodes : nullptr;
-        Q.closed = want_closed ? d_closed.p + at : nullptr;
-        HIPCHK(h, launch_wide_profile((int)W.net.K, dim3((uint32_t)wide_blocks(h, W, m, shmem)), shmem, h->stream, Q));
-    }
-    if (keep_states) {
-        keep_states->launches = launches;
-        return BSX_OK;
-    }
-    unsigned long long ctr[4] = {0, 0, 0, 0};
-    float ms = 0.f;
-    if (int rc = wide_timed_wait(h, W, ctr, ms)) return rc;
-    if (on_counts) HIPCHK(h, hipMemcpy(on_counts, d_on.p, n * n_nodes * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (states && state_words) HIPCHK(h, hipMemcpy(states, d_states.p, state_words * 8, hipMemcpyDeviceToHost));
-    if (closed) HIPCHK(h, hipMemcpy(closed, d_closed.p, n, hipMemcpyDeviceToHost));
-    put_stats(stats, n, sum_len, ctr[1], ms, launches, t_begin);
-    return BSX_OK;
 }
 
 // target: first hit time per problem into t_hit (kWideNone = none)

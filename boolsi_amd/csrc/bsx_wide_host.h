@@ -1,6 +1,7 @@
-// Private to the host files of the wide-state family (bsx_wide_api.cpp: network, space, simulate, target, profile;
-// bsx_wide_attract_api.cpp: bsx_run_attract_wide; bsx_wide_trans_api.cpp: bsx_run_attractor_transitions_wide): the
-// family's part of a handle, the kernel launch prototypes and the one launch setup all three share.
+// Private to the host files of the wide-state family (bsx_wide_api.cpp: network, space, simulate, target;
+// bsx_wide_attract_api.cpp: bsx_run_attract_wide; bsx_wide_trans_api.cpp: bsx_run_attractor_transitions_wide;
+// bsx_profile_api.cpp: the wide half of the profile stage): the family's part of a handle, the kernel launch prototypes
+// and the one launch setup they share.
 #pragma once
 #include "bsx_engine.h"
 #include "bsx_host.h"

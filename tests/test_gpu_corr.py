@@ -153,6 +153,15 @@ def frequencies(kind, n, seed=7):
 
 # ---- the comparison -------------------------------------------------------------------------------------------------------
 
+def corr_launches(n, n_nodes, wide):
+    """kernel_launches from include/bsx.h: one profile launch per BSX_PROFILE_CHUNK (wide: BSX_PROFILE_CHUNK_WIDE)
+    attractors; per column batch of 2^24 cells (BSX_CORR_BATCH_CELLS; at least one column) the observations, the sort
+    counted as one and the two rank walks; the covariance partials and their reduction"""
+    cells = int(os.environ.get('BSX_CORR_BATCH_CELLS', 0)) or 1 << 24
+    cols = max(1, min(n_nodes, min(cells, _lib.CORR_MAX_CELLS) // n))
+    return -(-n // (1 << 18 if wide else 1 << 22)) + 4 * -(-n_nodes // cols) + 2
+
+
 def check_table(eng, text, keys, lengths, freq, expect):
     """expect: set of 'nan' (a constant node), 'ties', 'lengths' (at least two), 'rho' (a pair with 0 < |rho| < 1)"""
     _, net, space = compiled(text)
@@ -174,6 +183,7 @@ def check_table(eng, text, keys, lengths, freq, expect):
 
     S, ranks, on, closed = eng.node_correlations(keys, lengths, freq, ranks=True, activity=True)
     assert eng.corr_stats['problems'] == n and eng.corr_stats['state_steps'] == sum(lengths)
+    assert eng.corr_stats['kernel_launches'] == corr_launches(n, m, eng.wide)
     assert closed.tolist() == [1] * n and np.array_equal(on, on_profile)
     assert np.array_equal(ranks, ref['ranks'])
     assert S.tobytes() == S.T.copy().tobytes()

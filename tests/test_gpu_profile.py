@@ -134,6 +134,8 @@ def check_against_references(eng, net, space, keys, lengths, with_states_from=Tr
     """one call for all attractors; on-counts, states, closed against the oracle walk and (optionally) states_from"""
     on, states, closed = eng.attractor_profile(keys, lengths)
     assert on.shape == (len(keys), net.n_nodes) and on.dtype == np.uint32 and len(states) == len(keys)
+    # one launch per BSX_PROFILE_CHUNK attractors, on the wide family per BSX_PROFILE_CHUNK_WIDE (include/bsx.h)
+    assert eng.profile_stats['kernel_launches'] == -(-len(keys) // (1 << 18 if eng.wide else 1 << 22)) == 1
     for q, (key, length) in enumerate(zip(keys, lengths)):
         want, back = oracle_walk(net, space, key, length)
         assert words_to_code(back) == key, 'reference: the key is not on a cycle of this length'

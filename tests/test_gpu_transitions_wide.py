@@ -467,6 +467,35 @@ def child_divergent(expected):
         assert e.trans_stats['kernel_launches'] == 4 + 4
 
 
+def wide_launches(n, flips, flip_chunk=1 << 22):
+    """kernel_launches on the wide family (include/bsx.h): one profile launch per BSX_PROFILE_CHUNK_WIDE rows, the rows'
+    walks in launches of 2^18, the build, one launch per flip_chunk flips (2^22, or BSX_WTRANS_CHUNK), the drain"""
+    return -(-n // (1 << 18)) + -(-n // (1 << 18)) + 1 + -(-flips // flip_chunk) + 1
+
+
+def test_three_launches_of_flips_in_a_child(tmp_path):
+    ref = wide_ref_of('n257')
+    flips = sum(ref.lengths) * len(ref.free)
+    chunk = -(-flips // 3)
+    assert -(-flips // chunk) == 3 and chunk % (32 * 16)                        # guard: three launches, none of whole groups
+    assert wide_launches(len(ref.keys), flips) == 5 and wide_launches(len(ref.keys), flips, chunk) == 7
+    n, seed, n_any, fixed, many = WIDE_CASES['n257']
+    handed = dict(plain(ref.transitions()), text=wide_text(n, seed, n_any, fixed, many), keys=[str(k) for k in ref.keys],
+                  lengths=ref.lengths, launches=7)
+    child('chunked', tmp_path, handed, {'BSX_WTRANS_CHUNK': str(chunk)})
+
+
+def child_chunked(handed):
+    net, space, _ = wide.compiled(handed['text'])
+    with Engine(0) as e:
+        e.set_problem(net, space)
+        assert e.wide
+        edges, exits, closed = e.attractor_transitions_wide([int(k) for k in handed['keys']], handed['lengths'], node_exits=True)
+        assert closed.tolist() == [1] * len(handed['keys'])
+        assert [list(t) for t in tuples(edges)] == handed['edges'] and exits.tolist() == handed['exits']
+        assert e.trans_stats['kernel_launches'] == handed['launches']
+
+
 def test_step_limit_in_a_child(tmp_path):
     child('step_limit', tmp_path, {}, {'BSX_WIDE': '1', 'BSX_WIDE_STEP_LIMIT': '512'})
 
@@ -493,5 +522,5 @@ if __name__ == '__main__':
     if case.startswith('agree_'):
         child_agree(case[len('agree_'):], handed)
     else:
-        {'divergent': child_divergent, 'step_limit': child_step_limit}[case](handed)
+        {'divergent': child_divergent, 'step_limit': child_step_limit, 'chunked': child_chunked}[case](handed)
     print(case + ' ok')
