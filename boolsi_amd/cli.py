@@ -131,6 +131,20 @@ def _listing(kw, cfg):
     return batch_layout(cfg['total combination count'], kw['reference_np'], kw['batches_per_process'])
 
 
+_seed_option = click.option(
+    '--seed', 'seed', type=click.IntRange(min=0, max=2 ** 64 - 1), default=None,
+    help='Seed of --samples: the same seed gives the same sample. Defaults to 0. An error without --samples.')
+
+
+def _check_sampling(kw, listing=False):
+    """--seed without --samples, and (simulate / target) --samples with a listing order of the reference."""
+    if kw['seed'] is not None and kw['samples'] is None:
+        raise click.UsageError('--seed needs --samples: without --samples every initial condition is enumerated.')
+    if listing and kw['samples'] is not None and kw['reference_np'] != 1:
+        raise click.UsageError('--reference-np cannot be combined with --samples: samples are listed in sample order, '
+                               'which no reference run produces.')
+
+
 @click.group()
 def cli():
     """BoolSi-compatible simulations of synchronous Boolean networks on AMD MI355X GPUs."""
@@ -140,7 +154,13 @@ def cli():
 @_common
 @click.option('-t', '--simulation-time', type=click.IntRange(min=1), required=True,
               help='(required) Number of time steps to simulate for.')
+@click.option('--samples', 'samples', type=click.IntRange(min=1),
+              help='Simulate this many sampled initial conditions (and variations) instead of all of them: '
+                   'for problem spaces too large to enumerate. Simulations are listed in sample order.')
+@_seed_option
 def simulate(**kw):
+    _check_sampling(kw, listing=True)
+
     def body(run):
         from .simulate import simulate_master
         from .output import output_simulations
@@ -148,7 +168,7 @@ def simulate(**kw):
         sims = simulate_master(run.open_engine(), cfg['origin simulation problem'],
                                cfg['simulation problem variations'], cfg['incoming node lists'],
                                cfg['truth tables'], kw['simulation_time'], cfg['total combination count'],
-                               comm=run.comm, listing=_listing(kw, cfg))
+                               comm=run.comm, listing=_listing(kw, cfg), samples=kw['samples'], seed=kw['seed'] or 0)
         if run.comm.rank == 0:
             output_simulations(sims, cfg['node names'], run.out)
     _guarded(kw, body)
@@ -176,11 +196,9 @@ def simulate(**kw):
 @click.option('--samples', 'samples', type=click.IntRange(min=1),
               help='Find attractors from this many sampled initial conditions (and variations) instead of all of them: '
                    'for problem spaces too large to enumerate. Frequencies are shares of the sample.')
-@click.option('--seed', 'seed', type=click.IntRange(min=0, max=2 ** 64 - 1), default=None,
-              help='Seed of --samples: the same seed gives the same sample. Defaults to 0. An error without --samples.')
+@_seed_option
 def attract(**kw):
-    if kw['seed'] is not None and kw['samples'] is None:
-        raise click.UsageError('--seed needs --samples: without --samples every initial condition is enumerated.')
+    _check_sampling(kw)
     def body(run):
         from .attract import attract_master, profile_attractors
         from .attractor_analysis import find_node_correlations, uses_device
@@ -232,7 +250,13 @@ def attract(**kw):
                    'state was not reached.')
 @click.option('-n', '--n-simulations-reaching-target', 'n_simulations_reaching_target', type=click.IntRange(min=1),
               help='Stop after this many simulations have reached target state.')
+@click.option('--samples', 'samples', type=click.IntRange(min=1),
+              help='Search this many sampled initial conditions (and variations) instead of all of them: '
+                   'for problem spaces too large to enumerate. -n keeps the first hits in sample order.')
+@_seed_option
 def target(**kw):
+    _check_sampling(kw, listing=True)
+
     def body(run):
         from .target import target_master
         from .output import output_simulations
@@ -243,7 +267,7 @@ def target(**kw):
                              cfg['simulation problem variations'], cfg['target substate code'],
                              cfg['target node set'], cfg['incoming node lists'], cfg['truth tables'],
                              n_to_find, max_t, cfg['total combination count'],
-                             comm=run.comm, listing=_listing(kw, cfg))
+                             comm=run.comm, listing=_listing(kw, cfg), samples=kw['samples'], seed=kw['seed'] or 0)
         if sims and run.comm.rank == 0:
             output_simulations(sims, cfg['node names'], run.out)
     _guarded(kw, body)

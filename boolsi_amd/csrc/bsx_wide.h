@@ -60,16 +60,22 @@ struct WideParams {
     uint64_t max_len;
     uint32_t* x0;               // scratch: [gridDim.x][rows * L] s(T_p) of the group
     unsigned long long* ctr;    // [0] reference steps, [1] executed trajectory updates, [2] step-limit hits
-    // sampled source (k_wide<K, KW, true> only; behind every field the other kernels read, so that their offsets stay)
+    // sampled source (the k_wide<K, KW, true, ...> instantiations only; behind every field the other kernels read, so that
+    // their offsets stay)
     uint64_t sample_k0;         // sample_k0(seed)
     uint64_t sample_first;      // first sample of this launch
     uint64_t sample_variants;   // V, the space's variant count (not saturated)
+    const uint64_t* sample_list;    // nullable, k_wide<K, KW, true, kWideSimulate> only: trajectory q is sample sample_list[q]
 };
 
-// ---- sampled problem source (k_wide_sampled / k_sample_problems in bsx_wide.hip, bsx_sample.h has the definition) ----
+// ---- sampled problem source (k_wide<K, KW, true, MODE> / k_sample_problems in bsx_wide.hip, bsx_sample.h has the
+// definition) ----
 // k_wide<K, KW, true> is k_wide's attract branch over samples [sample_first, sample_first + count) of a seed: trajectory k
 // of a group is sample sample_first + base + k.  Only a group's set-up differs (s(0) and the variant number come from the
 // generator, word by word, not from a decoded index); first_digits / first_variant / offsets are not read.
+// k_wide<K, KW, true, MODE> is the target or the simulate branch behind the same set-up; each sampled instantiation
+// carries the one branch of its mode.  With sample_list the simulate instantiation sets a group up per trajectory
+// (sample sample_list[base + k], with t_len / out_offsets of its own): lists are short, and that path is not tuned.
 // k_sample_problems: s(0) and the variant number of listed samples, one thread per sample
 struct WideSampleListParams {
     uint32_t n_nodes, w64, n_any, pad;

@@ -9,8 +9,9 @@
 //   * mu: a second lock-step pass, y = s(T_p + lambda_b) (bit b frozen after lambda_b steps) against x = s(T_p);
 //   * key: the minimum state over one lap of the cycle, by a bit-sliced lexicographic compare from the highest
 //     row down (per-slice lt / eq masks, combined across slices from the top).
-// k_wide_sampled is the attract branch over samples of a seed instead of consecutive problem indices (bsx_sample.h):
-// the same body, with the group's set-up chosen at compile time.
+// k_wide<K, KW, true> (attract) and k_wide<K, KW, true, MODE> (target, simulate) run over samples of a seed instead of
+// consecutive problem indices (bsx_sample.h): the same body, with the group's set-up and the one branch an instantiation
+// carries chosen at compile time.
 #include <hip/hip_runtime.h>
 
 #include "bsx_device.h"
@@ -130,10 +131,21 @@ __device__ __forceinline__ SampleColumn wide_sample_column(const uint32_t* keys,
 
 // KW: the network has nodes with more than 6 predecessors (their path's 32 table indices cost registers)
 // SAMPLED: trajectory k of a group is sample P.sample_first + base + k of the seed behind P.sample_k0 (bsx_sample.h), not
-// problem first + base + k; attract only.  A compile-time choice: it changes a group's set-up and nothing behind it.
-template <int K, bool KW, bool SAMPLED = false>
+// problem first + base + k.  A compile-time choice: it changes a group's set-up and nothing behind it.
+// MODE: the WideMode whose branch the instantiation carries, or -1 for all three, chosen by P.mode at run time (the
+// enumerating kernels).  A sampled instantiation carries one branch: k_wide<K, KW, true> is attract over samples, as it
+// was, k_wide<K, KW, true, kWideTarget / kWideSimulate> are target and simulate.  In the sampled simulate instantiation a
+// non-null P.sample_list makes trajectory q sample P.sample_list[q] (bsx_run_trajectories_sampled): set up per trajectory,
+// in the shape of the enumerating source, since a column's 32 samples are not consecutive there.
+// (One kernel template, not a shared body behind several: behind a forwarding kernel the enumerating instantiations came
+// out with other register and scratch figures.)
+template <int K, bool KW, bool SAMPLED = false, int MODE = SAMPLED ? (int)kWideAttract : -1>
 __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
+    static_assert(SAMPLED ? MODE >= 0 : MODE == -1, "a sampled instantiation carries one branch, an enumerating one all three");
     extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
+    constexpr bool kListable = SAMPLED && MODE == (int)kWideSimulate;
+    const bool listed = kListable && P.sample_list != nullptr;
+    const uint32_t mode = MODE < 0 ? P.mode : (uint32_t)MODE;
     WideCtx X;
     X.L = P.L;
     X.tid = threadIdx.x;
@@ -170,7 +182,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
         if (tid < 8) misc[tid] = 0;
         if constexpr (SAMPLED) {
             // the block keys of column tid's 32 samples (at most two blocks), once per group: col[4 tid ..], free until the warm-up
-            if (tid < L) {
+            if (tid < L && !listed) {
                 const SampleColumn sc = sample_column(P.sample_k0, P.sample_first + base + 32ull * tid);
                 col[4 * tid + 0] = (uint32_t)sc.kb0; col[4 * tid + 1] = (uint32_t)(sc.kb0 >> 32);
                 col[4 * tid + 2] = (uint32_t)sc.kb1; col[4 * tid + 3] = (uint32_t)(sc.kb1 >> 32);
@@ -180,7 +192,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
         if constexpr (SAMPLED) {
             // s(0): one word per ('any' ordinal, column), one plain store each (the origin has these rows cleared and
             // 'any' rows are distinct)
-            for (uint32_t i = tid; i < P.n_any * L; i += kWideThreads) {
+            for (uint32_t i = tid; i < (listed ? 0u : P.n_any * L); i += kWideThreads) {
                 const uint32_t a = i >> P.lshift, cw = i & (L - 1);
                 const SampleColumn sc = wide_sample_column(col, cw, P.sample_first + base + 32ull * cw);
                 const uint32_t n_bits = n_valid > 32 * cw ? (n_valid - 32 * cw < 32u ? n_valid - 32 * cw : 32u) : 0u;
@@ -194,7 +206,15 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
             } else {
                 uint64_t variant;
                 uint32_t bit, cw;
-                if constexpr (SAMPLED) {
+                if (listed) {
+                    // sample P.sample_list[base + k]: its own block key, one mix per 'any' ordinal, one atomicOr per set bit
+                    bit = 1u << (k & 31u); cw = k >> 5;
+                    const uint64_t j = P.sample_list[base + k];
+                    const uint64_t kb = sample_block_key(P.sample_k0, j >> 6);
+                    for (uint32_t a = 0; a < P.n_any; ++a)
+                        if (sample_any_bit(kb, a, j)) atomicOr(&B[0][P.any_nodes[a] * L + cw], bit);
+                    variant = sample_variant_of(kb, P.n_any, j, P.sample_variants);
+                } else if constexpr (SAMPLED) {
                     // sample first + base + k: the variant number is one draw of its own (the state bits are stored above)
                     bit = 1u << (k & 31u); cw = k >> 5;
                     const SampleColumn sc = wide_sample_column(col, cw, P.sample_first + base + 32ull * cw);
@@ -265,7 +285,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
         uint32_t* nxt = B[1];
         uint64_t group_steps = 0;
 
-        if (!SAMPLED && P.mode == kWideSimulate) {           // (the sampled source serves attract only)
+        if (mode == kWideSimulate) {
             // ---- s(0 .. T): trajectories as they pass, digest accumulators X / Y per row in B[2] / B[3]
             uint64_t T = P.max_t;
             if (P.t_len) {
@@ -322,7 +342,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(const WideParams P) {
                 for (uint32_t k = 0; k < n_valid; ++k) ref += P.t_len ? P.t_len[base + k] : P.max_t;
                 steps_ref += ref;
             }
-        } else if (!SAMPLED && P.mode == kWideTarget) {
+        } else if (mode == kWideTarget) {
             // ---- first t >= T_p with s(t) & mask == code (target.py:109-133); a trajectory whose cycle has closed
             //      (Brent from T_max = max T_p of the group, when every trajectory is autonomous) has shown all its
             //      states and ends without a hit
@@ -589,10 +609,18 @@ hipError_t launch_sample_problems(const WideSampleListParams& Q, hipStream_t st)
     return hipGetLastError();
 }
 
-// attract over samples of a seed (bsx_run_attract_sampled): k_wide's attract branch behind the sampled set-up
+// A call over samples of a seed (bsx_run_attract_sampled, bsx_run_target_sampled, bsx_run_simulate_sampled,
+// bsx_run_trajectories_sampled): the branch of Q.mode behind the sampled set-up
+template <int K, bool KW>
+static const void* wide_sampled_fn(uint32_t mode) {
+    if (mode == kWideTarget) return (const void*)k_wide<K, KW, true, (int)kWideTarget>;
+    if (mode == kWideSimulate) return (const void*)k_wide<K, KW, true, (int)kWideSimulate>;
+    return (const void*)k_wide<K, KW, true>;
+}
+
 template <int K>
 static hipError_t launch_wide_sampled_k(dim3 grid, size_t shmem, hipStream_t st, const WideParams& Q) {
-    const void* fn = Q.wdesc ? (const void*)k_wide<K, true, true> : (const void*)k_wide<K, false, true>;
+    const void* fn = Q.wdesc ? wide_sampled_fn<K, true>(Q.mode) : wide_sampled_fn<K, false>(Q.mode);
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return e;
     void* args[] = {const_cast<WideParams*>(&Q)};

@@ -123,13 +123,17 @@ int wide_enqueue(bsx_handle h, WideHost& W, WideParams& P, const bsx_index* firs
     return BSX_OK;
 }
 
-// The same over samples [first_sample, first_sample + count) of the seed behind k0 (attract; bsx_sample.h)
-int wide_enqueue_sampled(bsx_handle h, WideHost& W, WideParams& P, uint64_t k0, uint64_t first_sample, uint64_t count, uint64_t max_t) {
+// The same over samples [first_sample, first_sample + count) of the seed behind k0, or over the `count` listed ones
+// (bsx_sample.h); the kernel is the sampled instantiation of P.mode
+int wide_enqueue_sampled(bsx_handle h, WideHost& W, WideParams& P, uint64_t k0, uint64_t first_sample, uint64_t count, uint64_t max_t,
+                         const uint64_t* list) {
     uint64_t blocks = 0;
+    if (list && P.mode != kWideSimulate) return fail(h, BSX_ERR_INVALID, "listed samples are a source of simulate launches only");
     if (int rc = wide_fill_launch(h, W, P, count, max_t, &blocks)) return rc;
     P.sample_k0 = k0;
     P.sample_first = first_sample;
     P.sample_variants = W.space.variant_count;
+    P.sample_list = list;
     HIPCHK(h, launch_wide_sampled((int)W.net.K, dim3((uint32_t)blocks), W.space.shmem, h->stream, P));
     return BSX_OK;
 }
@@ -143,12 +147,27 @@ int wide_launch(bsx_handle h, WideHost& W, WideParams& P, const bsx_index* first
     return wide_timed_wait(h, W, ctr, ms);
 }
 
-static int wide_sim(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* offsets,
-                    const uint64_t* t_len, const uint64_t* out_offsets, uint64_t traj_words, uint64_t* trajectories,
-                    uint64_t* final_states, uint64_t* digests, bsx_stats* stats) {
+namespace {
+
+// consecutive problem indices from `first` (the enumerating calls)
+struct IndexRange : WideSource {
+    bsx_handle h; WideHost& W; const bsx_index* first; uint64_t max_t;
+    IndexRange(bsx_handle h_, WideHost& W_, const bsx_index* f, uint64_t t) : h(h_), W(W_), first(f), max_t(t) {}
+    int enqueue(WideParams& P, uint64_t done, uint64_t m) override {
+        const bsx_index at = index_plus(*first, done, h->sp.n_any);
+        return wide_enqueue(h, W, P, &at, m, max_t);
+    }
+};
+
+}  // namespace
+
+// simulate / trajectories over the `count` problems of one launch of `src` (listed: with offsets, lengths and places of
+// their own; `offsets` is null where the source has its own list)
+int wide_sim(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, uint64_t max_t, const uint64_t* offsets, const uint64_t* t_len,
+             const uint64_t* out_offsets, uint64_t traj_words, uint64_t* trajectories, uint64_t* final_states, uint64_t* digests,
+             bsx_stats* stats) {
     const double t_begin = now_ms();
     if (stats) std::memset(stats, 0, sizeof(*stats));
-    WideHost& W = *h->wide;
     if (count == 0) return BSX_OK;
     if (max_t >= kStepLimit) return fail(h, BSX_ERR_UNSUPPORTED, "simulation length above the engine's step limit");
     HIPCHK(h, hipSetDevice(h->device));
@@ -157,16 +176,22 @@ static int wide_sim(bsx_handle h, const bsx_index* first, uint64_t count, uint64
     WideParams P{};
     P.mode = kWideSimulate;
     if (trajectories) { HIPCHK(h, d_traj.alloc(traj_words)); P.traj = d_traj.p; }
+    // scattered trajectories: the whole buffer comes back in one copy, so the words between them make the round trip
+    // (a caller's buffer keeps what no trajectory covers, as in bsx_simulate_api.cpp)
+    if (trajectories && out_offsets) HIPCHK(h, hipMemcpy(d_traj.p, trajectories, traj_words * 8, hipMemcpyHostToDevice));
     if (final_states) { HIPCHK(h, d_final.alloc(count * w64)); P.final_states = d_final.p; }
     if (digests) { HIPCHK(h, d_dig.alloc(count)); P.digests = d_dig.p; }
-    if (offsets) {
-        HIPCHK(h, d_off.upload(std::vector<uint64_t>(offsets, offsets + count))); P.offsets = d_off.p;
+    if (offsets) { HIPCHK(h, d_off.upload(std::vector<uint64_t>(offsets, offsets + count))); P.offsets = d_off.p; }
+    if (t_len) {
         HIPCHK(h, d_tlen.upload(std::vector<uint64_t>(t_len, t_len + count))); P.t_len = d_tlen.p;
         HIPCHK(h, d_ooff.upload(std::vector<uint64_t>(out_offsets, out_offsets + count))); P.out_offsets = d_ooff.p;
     }
     unsigned long long ctr[4];
     float ms = 0.f;
-    if (int rc = wide_launch(h, W, P, first, count, max_t, ctr, ms)) return rc;
+    HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    if (int rc = src.enqueue(P, 0, count)) return rc;
+    if (int rc = wide_timed_wait(h, W, ctr, ms)) return rc;
     if (trajectories) HIPCHK(h, hipMemcpy(trajectories, d_traj.p, traj_words * 8, hipMemcpyDeviceToHost));
     if (final_states) HIPCHK(h, hipMemcpy(final_states, d_final.p, count * w64 * 8, hipMemcpyDeviceToHost));
     if (digests) HIPCHK(h, hipMemcpy(digests, d_dig.p, count * 8, hipMemcpyDeviceToHost));
@@ -176,7 +201,8 @@ static int wide_sim(bsx_handle h, const bsx_index* first, uint64_t count, uint64
 
 int wide_run_simulate(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, uint64_t* trajectories,
                       uint64_t* final_states, uint64_t* digests, bsx_stats* stats) {
-    return wide_sim(h, first, count, max_t, nullptr, nullptr, nullptr, trajectories ? count * (max_t + 1) * h->w64 : 0,
+    IndexRange src(h, *h->wide, first, max_t);
+    return wide_sim(h, *h->wide, src, count, max_t, nullptr, nullptr, nullptr, trajectories ? count * (max_t + 1) * h->w64 : 0,
                     trajectories, final_states, digests, stats);
 }
 
@@ -187,18 +213,18 @@ int wide_run_trajectories(bsx_handle h, const bsx_index* first, const uint64_t* 
         words = std::max(words, out_offsets[q] + (t_len[q] + 1) * h->w64);
         tmax = std::max(tmax, t_len[q]);
     }
-    return wide_sim(h, first, n, tmax, offsets, t_len, out_offsets, words, out, nullptr, nullptr, stats);
+    IndexRange src(h, *h->wide, first, tmax);
+    return wide_sim(h, *h->wide, src, n, tmax, offsets, t_len, out_offsets, words, out, nullptr, nullptr, stats);
 }
 
-// target: first hit time per problem into t_hit (kWideNone = none)
-static int wide_target_times(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
+// target: first hit time per problem of one launch of `src` over [done, done + count) into t_hit (kWideNone = none)
+static int wide_target_times(bsx_handle h, WideHost& W, WideSource& src, uint64_t done, uint64_t count, const uint64_t* mask_words,
                              const uint64_t* code_words, std::vector<uint32_t>& t_hit, bsx_stats* stats) {
     const double t_begin = now_ms();
     if (stats) std::memset(stats, 0, sizeof(*stats));
     t_hit.assign(count, kWideNone);
     if (count == 0) return BSX_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    WideHost& W = *h->wide;
     WideParams P{};
     P.mode = kWideTarget;
     wide_target_words(W.net.n, mask_words, code_words, P.tmask, P.tcode);
@@ -208,32 +234,37 @@ static int wide_target_times(bsx_handle h, const bsx_index* first, uint64_t coun
     P.t_hit = d_thit.p;
     unsigned long long ctr[4];
     float ms = 0.f;
-    if (int rc = wide_launch(h, W, P, first, count, max_t, ctr, ms)) return rc;
+    HIPCHK(h, hipMemsetAsync(W.d_ctr.p, 0, 4 * sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    if (int rc = src.enqueue(P, done, count)) return rc;
+    if (int rc = wide_timed_wait(h, W, ctr, ms)) return rc;
     HIPCHK(h, hipMemcpy(t_hit.data(), d_thit.p, count * 4, hipMemcpyDeviceToHost));
     put_stats(stats, count, ctr[0], ctr[1], ms, 1, t_begin);
     if (ctr[2]) return fail(h, BSX_ERR_STEP_LIMIT, "a trajectory reached the internal step limit");
     return BSX_OK;
 }
 
-// bsx_run_target, and bsx_run_target_summary under BSX_WIDE_HOST_REDUCE=1, on a wide network (the caller has checked the
-// arguments and zeroed the outputs; count > 0): the per-problem first-hit times come to the host in chunks of 2^24
-// problems (not BSX_WIDE_CHUNK) and are counted, binned and listed here.  list_all: a hit beyond `cap` is an error.
-static int wide_target_host(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
+// bsx_run_target, and the summary calls under BSX_WIDE_HOST_REDUCE=1 (the caller has checked the arguments and zeroed the
+// outputs; count > 0): the per-problem first-hit times come to the host in chunks of 2^24 problems (not BSX_WIDE_CHUNK)
+// and are counted, binned and listed here.  list_all: a hit beyond `cap` is an error.  The caller's arrays are written
+// only when the whole call succeeds.
+static int wide_target_host(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, const uint64_t* mask_words,
                             const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap, bool list_all,
                             uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats, double t_begin) {
     uint64_t total = 0, listed = 0;
     bsx_stats part{};
     if (stats) stats->problems = count;
+    std::vector<uint64_t> bins(hist_bins, 0);
+    std::vector<bsx_hit> list;
     for (uint64_t done = 0; done < count; done += 1ull << 24) {
         const uint64_t m = std::min<uint64_t>(1ull << 24, count - done);
-        const bsx_index at = index_plus(*first, done, h->sp.n_any);
         std::vector<uint32_t> t_hit;
-        if (int rc = wide_target_times(h, &at, m, max_t, mask_words, code_words, t_hit, &part)) return rc;
+        if (int rc = wide_target_times(h, W, src, done, m, mask_words, code_words, t_hit, &part)) return rc;
         for (uint64_t p = 0; p < m; ++p) {
             if (t_hit[p] == kWideNone) continue;
             ++total;
-            if (hist_bins) ++hist[std::min<uint64_t>(t_hit[p], hist_bins - 1)];
-            if (listed < cap) hits[listed++] = bsx_hit{done + p, t_hit[p]};
+            if (hist_bins) ++bins[std::min<uint64_t>(t_hit[p], hist_bins - 1)];
+            if (listed < cap) { list.push_back(bsx_hit{done + p, t_hit[p]}); ++listed; }
             else if (list_all) return fail(h, BSX_ERR_TABLE_FULL, "more hits than the caller's capacity (bsx_run_target_summary counts without listing)");
         }
         if (stats) {
@@ -241,6 +272,8 @@ static int wide_target_host(bsx_handle h, const bsx_index* first, uint64_t count
             stats->kernel_ms += part.kernel_ms; stats->kernel_launches += part.kernel_launches;
         }
     }
+    for (uint32_t b = 0; b < hist_bins; ++b) hist[b] = bins[b];
+    std::copy(list.begin(), list.end(), hits);
     *n_hits = total;
     if (n_listed) *n_listed = listed;
     if (stats) stats->total_ms = now_ms() - t_begin;
@@ -249,20 +282,21 @@ static int wide_target_host(bsx_handle h, const bsx_index* first, uint64_t count
 
 int wide_run_target(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
                     const uint64_t* code_words, bsx_hit* hits, uint64_t cap, uint64_t* n_hits, bsx_stats* stats, double t_begin) {
-    return wide_target_host(h, first, count, max_t, mask_words, code_words, nullptr, 0, hits, cap, true, n_hits, nullptr, stats, t_begin);
+    IndexRange src(h, *h->wide, first, max_t);
+    return wide_target_host(h, *h->wide, src, count, mask_words, code_words, nullptr, 0, hits, cap, true, n_hits, nullptr, stats, t_begin);
 }
 
-// bsx_run_target_summary on a wide network (the caller has checked the arguments and zeroed the outputs; count > 0).
-// On the device: k_wide_reduce_target counts and bins every chunk's t_hit right behind the k_wide launch that wrote
-// it.  A chunk's t_hit is copied to the host only while the caller's hit list has room; with cap == 0, or once the
-// list is full, the host waits once, at the end.  Chunks are 2^24 problems, or BSX_WIDE_CHUNK.
-int wide_run_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
-                            const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
-                            uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats, double t_call) {
+// bsx_run_target_summary on a wide network and bsx_run_target_sampled (the caller has checked the arguments and zeroed the
+// outputs; count > 0), over the launches of `src`.  On the device: k_wide_reduce_target counts and bins every chunk's t_hit
+// right behind the k_wide launch that wrote it.  A chunk's t_hit is copied to the host only while the caller's hit list
+// has room; with cap == 0, or once the list is full, the host waits once, at the end.  Chunks are 2^24 problems, or
+// BSX_WIDE_CHUNK.
+int wide_target_summary(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, const uint64_t* mask_words,
+                        const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
+                        uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats, double t_call) {
     if (h->knobs.wide_host_reduce)
-        return wide_target_host(h, first, count, max_t, mask_words, code_words, hist, hist_bins, hits, cap, false, n_hits, n_listed, stats, t_call);
+        return wide_target_host(h, W, src, count, mask_words, code_words, hist, hist_bins, hits, cap, false, n_hits, n_listed, stats, t_call);
     const double t_begin = now_ms();
-    WideHost& W = *h->wide;
     WideParams P0{};
     P0.mode = kWideTarget;
     wide_target_words(W.net.n, mask_words, code_words, P0.tmask, P0.tcode);
@@ -291,12 +325,11 @@ int wide_run_target_summary(bsx_handle h, const bsx_index* first, uint64_t count
     };
     for (uint64_t done = 0; done < count; done += chunk) {
         const uint64_t m = std::min(chunk, count - done);
-        const bsx_index at = index_plus(*first, done, h->sp.n_any);
         HIPCHK(h, hipMemsetAsync(W.d_thit.p, 0xFF, m * 4, h->stream));
         if (!timing) { HIPCHK(h, hipEventRecord(h->ev0, h->stream)); timing = true; }
         WideParams P = P0;
         P.t_hit = W.d_thit.p;
-        if (int rc = wide_enqueue(h, W, P, &at, m, max_t)) return rc;
+        if (int rc = src.enqueue(P, done, m)) return rc;
         HIPCHK(h, launch_wide_reduce_target(W.d_thit.p, m, W.d_hist.p, hist_bins, W.d_out.p, h->stream));
         launches += 2;
         if (listed < cap) {                     // the list still has room: this chunk's hit times, in index order
@@ -321,6 +354,13 @@ int wide_run_target_summary(bsx_handle h, const bsx_index* first, uint64_t count
     std::copy(list.begin(), list.end(), hits);
     if (n_listed) *n_listed = listed;
     return BSX_OK;
+}
+
+int wide_run_target_summary(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t, const uint64_t* mask_words,
+                            const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
+                            uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats, double t_call) {
+    IndexRange src(h, *h->wide, first, max_t);
+    return wide_target_summary(h, *h->wide, src, count, mask_words, code_words, hist, hist_bins, hits, cap, n_hits, n_listed, stats, t_call);
 }
 
 }  // namespace bsx

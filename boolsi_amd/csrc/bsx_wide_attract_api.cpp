@@ -1,7 +1,7 @@
 // bsx_run_attract_wide: attract over the wide-state family's per-problem records, aggregated by key -- on the device
 // (bsx_wide_reduce.hip) or, with BSX_WIDE_HOST_REDUCE=1 or a table beyond kWideReduceMaxCap, chunk by chunk on the host
 // (the path before bsx_wide_reduce.hip; kept for A/B runs and tests).  Both legs take the source of their launches as
-// an argument (WideAttractSource, bsx_wide_host.h): bsx_run_attract_sampled (bsx_sample_api.cpp) runs them over samples.
+// an argument (WideSource, bsx_wide_host.h): bsx_run_attract_sampled (bsx_sample_api.cpp) runs them over samples.
 #include <algorithm>
 #include <array>
 #include <cstring>
@@ -45,7 +45,7 @@ static WideParams attract_params(uint32_t* d_info, uint64_t* d_keys, uint64_t ma
 // kInlineRecs records come back with the header in that one copy; a table with more costs a second copy.
 static constexpr uint32_t kInlineRecs = 256;
 
-int bsx::attract_wide_device(bsx_handle h, WideHost& W, WideAttractSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
+int bsx::attract_wide_device(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
                              bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor, bsx_stats2* stats,
                              double t_begin) {
     const uint32_t w64 = W.net.w64;
@@ -106,7 +106,7 @@ int bsx::attract_wide_device(bsx_handle h, WideHost& W, WideAttractSource& src, 
 }
 
 // Host path: every chunk's records come back and are aggregated here by key; one launch and one wait per chunk.
-int bsx::attract_wide_host(bsx_handle h, WideHost& W, WideAttractSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
+int bsx::attract_wide_host(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
                            bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor, bsx_stats2* stats,
                            double t_begin) {
     const uint32_t w64 = W.net.w64;
@@ -204,7 +204,7 @@ extern "C" int bsx_run_attract_wide(bsx_handle h, bsx_u128 first_flat, bsx_u128 
     // (more than kWideReduceMaxCap possible attractors: the device table would take gigabytes; such a call is reduced
     // on the host, which allocates per attractor found)
     const bool on_device = !h->knobs.wide_host_reduce && std::min<uint64_t>(cap, count) <= kWideReduceMaxCap;
-    struct Range : WideAttractSource {      // consecutive problem indices from `first`
+    struct Range : WideSource {      // consecutive problem indices from `first`
         bsx_handle h; WideHost& W; const bsx_index& first; uint64_t max_t;
         Range(bsx_handle h_, WideHost& W_, const bsx_index& f, uint64_t t) : h(h_), W(W_), first(f), max_t(t) {}
         int enqueue(WideParams& P, uint64_t done, uint64_t m) override {

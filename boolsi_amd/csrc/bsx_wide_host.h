@@ -78,11 +78,14 @@ int wide_upload_network(bsx_handle h, WideHost& W, uint32_t n_nodes, const uint3
 int wide_upload_space(bsx_handle h, WideHost& W, const uint64_t* origin_state_words, const uint32_t* any_nodes, uint32_t n_any,
                       const bsx_fixed* fixed, uint32_t n_fixed, const bsx_fixed_var* fixed_var, uint32_t n_fixed_var,
                       const bsx_pert* sched, uint32_t n_sched, const bsx_pert_var* pert_var, uint32_t n_pert_var);
-// bsx_wide_api.cpp: one k_wide launch enqueued; one launch waited for; one k_wide_sampled launch enqueued
+// bsx_wide_api.cpp: one k_wide launch enqueued; one launch waited for; one launch over samples enqueued
 int wide_enqueue(bsx_handle h, WideHost& W, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t);
 int wide_launch(bsx_handle h, WideHost& W, WideParams& P, const bsx_index* first, uint64_t count, uint64_t max_t,
                 unsigned long long (&ctr)[4], float& ms);
-int wide_enqueue_sampled(bsx_handle h, WideHost& W, WideParams& P, uint64_t k0, uint64_t first_sample, uint64_t count, uint64_t max_t);
+// (the sampled launch carries the branch of P.mode; with `list` -- device memory, `count` sample numbers -- trajectory q is
+// sample list[q]: simulate only)
+int wide_enqueue_sampled(bsx_handle h, WideHost& W, WideParams& P, uint64_t k0, uint64_t first_sample, uint64_t count, uint64_t max_t,
+                         const uint64_t* list = nullptr);
 // An enumerating call on a space with more 'any' nodes than a bsx_index holds (only the sampled calls reach such a space).
 // The calls that take a bsx_index are refused by check_range (bsx_host.h); this is the same refusal for the flat index
 // of bsx_run_attract_wide, in front of its split.
@@ -92,16 +95,26 @@ inline int wide_check_enumerable(bsx_handle h, const WideHost& W) {
     return BSX_OK;
 }
 
-// bsx_wide_attract_api.cpp: the two legs of an attract call over `count` problems in launches of `chunk`, behind
-// bsx_run_attract_wide and bsx_run_attract_sampled.  The source enqueues the launch over problems [done, done + m) of the
-// call (consecutive indices, or samples of a seed); everything behind the launch is the same for both.
-struct WideAttractSource {
+// The source of a call's launches: it enqueues the launch over problems [done, done + m) of the call (consecutive indices,
+// or samples of a seed); everything behind the launch is the same for both.
+struct WideSource {
     virtual int enqueue(WideParams& P, uint64_t done, uint64_t m) = 0;
-    virtual ~WideAttractSource() = default;
+    virtual ~WideSource() = default;
 };
-int attract_wide_device(bsx_handle h, WideHost& W, WideAttractSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
+// bsx_wide_api.cpp: simulate / trajectories as one launch of `src` (t_len / out_offsets: listed trajectories; offsets: their
+// problems where the source enumerates), and the target summary's chain over its launches (bsx_run_target_summary on a wide
+// network, bsx_run_target_sampled); the callers have checked the arguments and zeroed the outputs
+int wide_sim(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, uint64_t max_t, const uint64_t* offsets, const uint64_t* t_len,
+             const uint64_t* out_offsets, uint64_t traj_words, uint64_t* trajectories, uint64_t* final_states, uint64_t* digests,
+             bsx_stats* stats);
+int wide_target_summary(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, const uint64_t* mask_words,
+                        const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
+                        uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats, double t_call);
+// bsx_wide_attract_api.cpp: the two legs of an attract call over `count` problems in launches of `chunk`, behind
+// bsx_run_attract_wide and bsx_run_attract_sampled.
+int attract_wide_device(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
                         bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor, bsx_stats2* stats, double t_begin);
-int attract_wide_host(bsx_handle h, WideHost& W, WideAttractSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
+int attract_wide_host(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,
                       bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out, bsx_u128* n_no_attractor, bsx_stats2* stats, double t_begin);
 
 }  // namespace bsx

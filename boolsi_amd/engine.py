@@ -37,6 +37,25 @@ def key_to_int(key_words):
     return v
 
 
+def flat_indices(states, variants, any_nodes):
+    """
+    Flat problem indices I = bits + (variant << n_any) of batching.py:212-229 (what problem_from_index takes), as Python
+    ints, from what bsx_sample_problems returns: states (n, W) uint64 = s(0), variants (n,) uint64; bit a of `bits` is
+    the state of the a-th 'any' node, any_nodes[a], in s(0).
+    """
+    if len(variants) == 0:
+        return []
+    states = np.asarray(states, np.uint64).reshape(len(variants), -1)
+    any_nodes = np.asarray(any_nodes, np.int64)
+    n_any = len(any_nodes)
+    if n_any == 0:
+        return [int(v) for v in np.asarray(variants, np.uint64).tolist()]
+    bits = (states[:, any_nodes >> 6] >> (any_nodes & 63).astype(np.uint64)) & np.uint64(1)
+    packed = np.packbits(bits.astype(np.uint8), axis=1, bitorder='little')
+    return [int.from_bytes(row.tobytes(), 'little') | (int(v) << n_any)
+            for row, v in zip(packed, np.asarray(variants, np.uint64).tolist())]
+
+
 class Engine:
     def __init__(self, device=0):
         self._lib = _lib.load()
@@ -374,6 +393,53 @@ class Engine:
         variants = np.zeros(len(samples), np.uint64)
         self._check(self._lib.bsx_sample_problems(self._h, int(seed), ptr(samples), len(samples), ptr(states), ptr(variants)))
         return states, variants
+
+    def sample_flat_indices(self, seed, samples):
+        """Flat problem indices of the listed samples of `seed` (flat_indices over sample_problems), as Python ints."""
+        states, variants = self.sample_problems(seed, samples)
+        return flat_indices(states, variants, self.space.any_nodes)
+
+    def target_sampled(self, seed, first, count, max_t, mask_words, code_words, hist_bins=0, cap=0):
+        """bsx_run_target_sampled: target_summary over samples [first, first + count) of `seed`
+        -> (n_hits, histogram of first-hit times (last bin = that time or later), the first min(n_hits, cap) hits in
+        sample order with offset = sample - first, stats)."""
+        hist = np.zeros(max(hist_bins, 1), np.uint64)
+        hits = np.zeros(max(cap, 1), _lib.HIT)
+        m = np.ascontiguousarray(mask_words, np.uint64)
+        c = np.ascontiguousarray(code_words, np.uint64)
+        n_hits, n_listed = C.c_uint64(), C.c_uint64()
+        st = Stats()
+        self._check(self._lib.bsx_run_target_sampled(
+            self._h, int(seed), int(first), int(count), _cap(max_t), ptr(m), ptr(c), ptr(hist) if hist_bins else None,
+            hist_bins, ptr(hits) if cap else None, cap, C.byref(n_hits), C.byref(n_listed), C.byref(st)))
+        return n_hits.value, hist[:hist_bins], hits[:n_listed.value], st.as_dict()
+
+    def simulate_sampled(self, seed, first, count, max_t, trajectories=True, final=True, digest=True):
+        """bsx_run_simulate_sampled: simulate over samples [first, first + count) of `seed`."""
+        W = self.net.n_words
+        traj = np.zeros((count, max_t + 1, W), np.uint64) if trajectories else None
+        fin = np.zeros((count, W), np.uint64) if final else None
+        dig = np.zeros(count, np.uint64) if digest else None
+        st = Stats()
+        self._check(self._lib.bsx_run_simulate_sampled(self._h, int(seed), int(first), int(count), int(max_t),
+                                                       ptr(traj) if trajectories else None, ptr(fin) if final else None,
+                                                       ptr(dig) if digest else None, C.byref(st)))
+        return traj, fin, dig, st.as_dict()
+
+    def trajectories_sampled(self, seed, samples, t_len):
+        """States s(0..t_len[q]) of samples samples[q] of `seed` -> list of (t_len[q] + 1, W) arrays."""
+        W = self.net.n_words
+        samples = np.ascontiguousarray(samples, np.uint64)
+        t_len = np.ascontiguousarray(t_len, np.uint64)
+        sizes = (t_len + np.uint64(1)) * np.uint64(W)
+        out_off = np.zeros(len(samples), np.uint64)
+        if len(samples) > 1:
+            out_off[1:] = np.cumsum(sizes[:-1])
+        out = np.zeros(int(sizes.sum()), np.uint64)
+        st = Stats()
+        self._check(self._lib.bsx_run_trajectories_sampled(self._h, int(seed), ptr(samples), ptr(t_len), len(samples),
+                                                           ptr(out), ptr(out_off), C.byref(st)))
+        return [out[int(o):int(o) + int(s)].reshape(-1, W) for o, s in zip(out_off, sizes)], st.as_dict()
 
     def target(self, first, count, max_t, mask_words, code_words, cap=None):
         cap = count if cap is None else cap

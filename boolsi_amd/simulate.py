@@ -39,16 +39,25 @@ def states_from_words(traj, n_nodes):
 
 
 def simulate_master(engine, origin_simulation_problem, simulation_problem_variations,
-                    predecessor_node_lists, truth_tables, max_t, n_simulation_problems, comm=None, listing=None):
+                    predecessor_node_lists, truth_tables, max_t, n_simulation_problems, comm=None, listing=None,
+                    samples=None, seed=0):
     """
     -> list of Simulation (on rank 0; other ranks get []).  Order: problem-index order, which is the
     order of a single-process reference run; with `listing` (batching.BatchLayout) the order in which a
     multi-process reference run with that layout lists them (batch number, place in batch).
     With more than one rank the index range is partitioned and the trajectories all-gathered.
+    samples = N: samples 0 .. N - 1 of `seed` (include/bsx.h defines them; bsx_run_simulate_sampled) are simulated instead
+    of the whole space and listed in sample order (no listing).
     """
     from .dist import Comm, partition
     comm = comm or Comm()
     log = logging.getLogger()
+    sampled = samples is not None
+    if sampled:
+        if listing is not None:
+            raise ValueError('a listing order of the reference has no meaning for samples')
+        log.info('Sampling {} initial conditions out of {} with seed {}.'.format(samples, n_simulation_problems, seed))
+        n_simulation_problems = samples
     if comm.world == 1:
         log.info('Single process will be used to perform {} simulations...'.format(n_simulation_problems))
     else:
@@ -66,7 +75,10 @@ def simulate_master(engine, origin_simulation_problem, simulation_problem_variat
     parts = []
     for first in range(lo, lo + mine, TILE):
         count = min(TILE, lo + mine - first)
-        traj, _, _, _ = engine.simulate(first, count, max_t, trajectories=True, final=False, digest=False)
+        if sampled:
+            traj, _, _, _ = engine.simulate_sampled(seed, first, count, max_t, trajectories=True, final=False, digest=False)
+        else:
+            traj, _, _, _ = engine.simulate(first, count, max_t, trajectories=True, final=False, digest=False)
         parts.append(traj)
     local = np.concatenate(parts) if parts else np.zeros((0, max_t + 1, net.n_words), np.uint64)
     trajs = comm.gather_concat(local)
@@ -75,10 +87,14 @@ def simulate_master(engine, origin_simulation_problem, simulation_problem_variat
     numeral_system = create_numeral_system_from_variations(simulation_problem_variations)
     from .batching import reference_order
     order = reference_order(listing) if listing is not None else range(n_simulation_problems)
+    problem_of = range(n_simulation_problems)
+    if sampled:             # the problem behind sample j is its flat index
+        problem_of = [i for lo in range(0, samples, 1 << 16)
+                      for i in engine.sample_flat_indices(seed, range(lo, min(samples, lo + (1 << 16))))]
     simulations = []
     for index in order:
         _, fixed_nodes, perturbed_nodes_by_t = problem_from_index(
-            index, origin_simulation_problem, simulation_problem_variations, numeral_system)
+            problem_of[index], origin_simulation_problem, simulation_problem_variations, numeral_system)
         simulations.append(Simulation(states_from_words(trajs[index], n_nodes), fixed_nodes, perturbed_nodes_by_t))
     return simulations
 

@@ -7,6 +7,10 @@ trajectory closes its cycle or max_t comes first); the states of the hits are th
 with bsx_run_trajectories.  `-n` keeps the first n hits in enumeration (= index) order, exactly
 what the reference's single process finds before it stops (simulate.py:163-164, mpi.py:537-538):
 index tiles are processed in order and the search stops after the tile that completes n.
+
+`samples = N` searches samples 0 .. N - 1 of a seed instead (include/bsx.h defines them; bsx_run_target_sampled,
+bsx_run_trajectories_sampled), for problem spaces too large to enumerate: the order is sample order, `-n` keeps the first
+n hits in it, and the hits are counted against N.
 """
 import logging
 from math import inf
@@ -22,13 +26,17 @@ from .simulate import Simulation, states_from_words, MAX_STATE_CELLS
 TILE = 1 << 24
 
 
-def find_hits(engine, first, count, max_t, mask, code, n_to_find=inf):
+def find_hits(engine, first, count, max_t, mask, code, n_to_find=inf, seed=None):
     """(offset from `first`, t) of the hits in [first, first + count), index order, stopping after the
-    tile that completes n_to_find.  Returns (hits array of _lib.HIT, problems scanned)."""
+    tile that completes n_to_find.  Returns (hits array of _lib.HIT, problems scanned).
+    With `seed`, [first, first + count) are sample numbers of that seed, and the order is sample order."""
     found, scanned, n = [], 0, 0
     while scanned < count and n < n_to_find:
         tile = min(TILE, count - scanned)
-        hits, _ = engine.target(first + scanned, tile, max_t, mask, code)
+        if seed is None:
+            hits, _ = engine.target(first + scanned, tile, max_t, mask, code)
+        else:
+            _, _, hits, _ = engine.target_sampled(seed, first + scanned, tile, max_t, mask, code, cap=tile)
         if len(hits):
             hits = hits.copy()
             hits['offset'] += np.uint64(scanned)
@@ -39,12 +47,13 @@ def find_hits(engine, first, count, max_t, mask, code, n_to_find=inf):
     return out, scanned
 
 
-def target_hits_partitioned(engine, max_t, mask, code, n_simulation_problems, comm=None):
+def target_hits_partitioned(engine, max_t, mask, code, n_simulation_problems, comm=None, seed=None):
     """Range-partitioned search over all problems (one rank per GPU); every rank gets all hits, in
-    index order (rank order = index order).  Problem indices here must fit 64 bits."""
+    index order (rank order = index order).  Problem indices here must fit 64 bits.
+    With `seed`: over samples 0 .. n_simulation_problems - 1 of that seed, in sample order."""
     comm = comm or Comm()
     first, count = partition(n_simulation_problems, comm.world, comm.rank)
-    hits, _ = find_hits(engine, first, count, max_t, mask, code)
+    hits, _ = find_hits(engine, first, count, max_t, mask, code, seed=seed)
     hits = hits.copy()
     hits['offset'] += np.uint64(first)
     return comm.gather_concat(hits)
@@ -52,7 +61,8 @@ def target_hits_partitioned(engine, max_t, mask, code, n_simulation_problems, co
 
 def target_master(engine, origin_simulation_problem, simulation_problem_variations,
                   target_substate_code, target_node_set, predecessor_node_lists, truth_tables,
-                  n_simulations_to_reach_target_substate, max_t, n_simulation_problems, comm=None, listing=None):
+                  n_simulations_to_reach_target_substate, max_t, n_simulation_problems, comm=None, listing=None,
+                  samples=None, seed=0):
     """
     -> list of Simulation (states s(0..t_hit)) on rank 0, [] elsewhere; log lines as target.py:45-86.
     Order: index order = single-process reference order; with `listing` (batching.BatchLayout) the
@@ -61,9 +71,17 @@ def target_master(engine, origin_simulation_problem, simulation_problem_variatio
     Single rank, index order: tiles are searched in order and the search stops after the tile that
     completes n.  Several ranks or a listing: the whole space is searched (range-partitioned), hits
     all-gathered, ordered, cut to n, and materialised by rank 0.
+    samples = N: samples 0 .. N - 1 of `seed` are searched instead of the whole space, in sample order (no listing);
+    the log lines then count against N.
     """
     log = logging.getLogger()
     comm = comm or Comm()
+    sampled = samples is not None
+    if sampled:
+        if listing is not None:
+            raise ValueError('a listing order of the reference has no meaning for samples')
+        log.info('Sampling {} initial conditions out of {} with seed {}.'.format(samples, n_simulation_problems, seed))
+        n_simulation_problems = samples
     n_to_find = n_simulations_to_reach_target_substate
     if n_to_find is not inf and n_to_find > n_simulation_problems:
         log.warning('Requested {} simulations that reach target state, but only {} simulation '
@@ -83,9 +101,9 @@ def target_master(engine, origin_simulation_problem, simulation_problem_variatio
 
     scanned = n_simulation_problems
     if comm.world == 1 and listing is None:
-        hits, scanned = find_hits(engine, 0, n_simulation_problems, max_t, mask, code, n_to_find)
+        hits, scanned = find_hits(engine, 0, n_simulation_problems, max_t, mask, code, n_to_find, seed=seed if sampled else None)
     else:
-        hits = target_hits_partitioned(engine, max_t, mask, code, n_simulation_problems, comm)
+        hits = target_hits_partitioned(engine, max_t, mask, code, n_simulation_problems, comm, seed=seed if sampled else None)
         if listing is not None and len(hits):
             keys = [listing.position(int(i)) for i in hits['offset']]
             hits = hits[sorted(range(len(hits)), key=keys.__getitem__)]
@@ -103,10 +121,15 @@ def target_master(engine, origin_simulation_problem, simulation_problem_variatio
     simulations = []
     for lo in range(0, len(hits), 1 << 16):
         part = hits[lo:lo + (1 << 16)]
-        trajs, _ = engine.trajectories(0, part['offset'], part['t'])
-        for h, traj in zip(part, trajs):
+        if sampled:         # offsets are sample numbers; the problem behind each is its flat index
+            trajs, _ = engine.trajectories_sampled(seed, part['offset'], part['t'])
+            indices = engine.sample_flat_indices(seed, part['offset'])
+        else:
+            trajs, _ = engine.trajectories(0, part['offset'], part['t'])
+            indices = [int(o) for o in part['offset']]
+        for index, traj in zip(indices, trajs):
             _, fixed_nodes, perturbed_nodes_by_t = problem_from_index(
-                int(h['offset']), origin_simulation_problem, simulation_problem_variations, numeral_system)
+                index, origin_simulation_problem, simulation_problem_variations, numeral_system)
             simulations.append(Simulation(states_from_words(traj, n_nodes), fixed_nodes, perturbed_nodes_by_t))
 
     # (no "Goal reached at ..." line: the reference's single process never prints it, because

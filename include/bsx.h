@@ -232,7 +232,7 @@ int  bsx_run_attract_wide(bsx_handle h, bsx_u128 first, bsx_u128 count,
                           bsx_attr_rec2w* table, uint32_t cap, uint32_t* n_out,
                           bsx_u128* n_no_attractor, bsx_stats2* stats);
 
-/* ---- attract over sampled initial conditions (no reference analogue: the reference enumerates) -------------------------
+/* ---- attract, target and simulate over sampled initial conditions (no reference analogue: the reference enumerates) ----
  * For spaces too large to enumerate.  Sample j of seed `seed` is a problem of the current space; this definition is
  * NORMATIVE, part of the ABI, and implemented in boolsi_amd/csrc/bsx_sample.h.  All arithmetic is mod 2^64.
  *
@@ -252,7 +252,7 @@ int  bsx_run_attract_wide(bsx_handle h, bsx_u128 first, bsx_u128 count,
  * samples of a seed are n independent draws, the first n indices of a space vary its low digits only.
  *
  * On the wide family a space may have up to n 'any' nodes.  With more than a bsx_index holds (64 * BSX_MAX_WORDS) only the
- * two calls below (and profile, correlations, transitions, which do not read the 'any' nodes) work on it; every entry
+ * sampled calls below (and profile, correlations, transitions, which do not read the 'any' nodes) work on it; every entry
  * point that takes a bsx_index or a flat index returns BSX_ERR_UNSUPPORTED.  A space whose variant count does not fit
  * 64 bits is BSX_ERR_UNSUPPORTED here as everywhere. */
 
@@ -266,6 +266,33 @@ int  bsx_run_attract_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample,
 /* the problems behind listed sample numbers: states[q * W + w] = s(0) of sample samples[q], variants[q] (nullable) */
 int  bsx_sample_problems(bsx_handle h, uint64_t seed, const uint64_t* samples, uint64_t n,
                          uint64_t* states, uint64_t* variants);
+
+/* target and simulate over samples.  The three calls work on handles of both families with the
+ * same results (the second lowering of bsx_run_attract_sampled), on spaces with up to n 'any' nodes, and are pure
+ * functions of (seed, first_sample, n_samples) that add up over disjoint ranges.  BSX_ERR_INVALID if first_sample +
+ * n_samples wraps, BSX_ERR_STATE without a network or a problem space, BSX_ERR_UNSUPPORTED for a space whose variant count
+ * does not fit 64 bits.
+ *
+ * bsx_run_target_sampled: bsx_run_target_summary over samples [first_sample, first_sample + n_samples).  *n_hits is exact;
+ * hist[b] = samples whose first hit is at t == b for b < hist_bins - 1, hist[hist_bins - 1] = at that time or later
+ * (hist_bins may be 0, at most 2048); hits[0..*n_listed) = the first min(*n_hits, cap) hits in ascending sample order,
+ * hits[].offset = sample - first_sample; cap may be 0, and then the host waits for the device once.  Times, state_steps
+ * and the step limit are those of bsx_run_target_summary on a wide network: a trajectory that reaches the step limit
+ * undecided (max_t BSX_T_INF, or at or beyond the limit of 2^24 lock steps / BSX_WIDE_STEP_LIMIT) makes the call return
+ * BSX_ERR_STEP_LIMIT, and hist / hits are written only by a call that succeeds.  At most 2^40 samples per call. */
+int  bsx_run_target_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample, uint64_t n_samples, uint64_t max_t,
+                            const uint64_t* mask_words, const uint64_t* code_words,
+                            uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
+                            uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats);
+/* bsx_run_simulate over samples [first_sample, first_sample + n_samples): the same three sinks (any may be NULL), layouts
+ * and digest, p = sample - first_sample; a max_t at or above the step limit (2^30) is BSX_ERR_UNSUPPORTED. */
+int  bsx_run_simulate_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample, uint64_t n_samples, uint64_t max_t,
+                              uint64_t* trajectories, uint64_t* final_states, uint64_t* digests, bsx_stats* stats);
+/* bsx_run_trajectories over listed samples: s(0..t_len[q]) of sample samples[q] (any 64-bit sample numbers, in any order)
+ * at out[out_offsets[q] ..); used to materialise the simulations of sampled target hits.  Words of `out` that no
+ * trajectory covers keep their value. */
+int  bsx_run_trajectories_sampled(bsx_handle h, uint64_t seed, const uint64_t* samples, const uint64_t* t_len, uint64_t n,
+                                  uint64_t* out, const uint64_t* out_offsets, bsx_stats* stats);
 
 /* target (target.py:109-133): hits in ascending offset order into hits[0..*n_hits); mask/code are W words
  * (target node set / target substate code, input.py:580-661). */
