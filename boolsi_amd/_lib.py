@@ -25,7 +25,7 @@ EXPORTS = (
     'bsx_set_network', 'bsx_set_problem_space', 'bsx_run_attract', 'bsx_run_attract2', 'bsx_run_attract_wide', 'bsx_run_attract_fgraph', 'bsx_run_target',
     'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_run_attractor_profile', 'bsx_run_node_correlations', 'bsx_run_attractor_transitions', 'bsx_run_attractor_transitions_wide',
     'bsx_run_attract_sampled', 'bsx_sample_problems',
-    'bsx_run_target_sampled', 'bsx_run_simulate_sampled', 'bsx_run_trajectories_sampled',
+    'bsx_run_target_sampled', 'bsx_run_simulate_sampled', 'bsx_run_trajectories_sampled', 'bsx_run_damage_sampled',
     'bsx_synchronize',
     'bsx_comm_unique_id', 'bsx_comm_init', 'bsx_comm_allgather', 'bsx_comm_destroy',
 )
@@ -154,6 +154,7 @@ def load():
                                            C.POINTER(Stats)]
     lib.bsx_run_simulate_sampled.argtypes = [vp, u64, u64, u64, u64, vp, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_trajectories_sampled.argtypes = [vp, u64, vp, vp, u64, vp, vp, C.POINTER(Stats)]
+    lib.bsx_run_damage_sampled.argtypes = [vp, u64, u64, u64, u32, u32, vp, vp, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_attract_fgraph.argtypes = [vp, C.POINTER(Index), u64, u64, u64, vp, u32, C.POINTER(u32),
                                            C.POINTER(u64), C.POINTER(Stats)]
     lib.bsx_run_target.argtypes = [vp, C.POINTER(Index), u64, u64, vp, vp, vp, u64, C.POINTER(u64),

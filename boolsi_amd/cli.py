@@ -1,6 +1,7 @@
 """
 Command line: `python -m boolsi_amd simulate|attract|target FILE [options]`, same commands and
-option names as the reference's `boolsi` script (`boolsi/cli.py:35-63, 184-328`).
+option names as the reference's `boolsi` script (`boolsi/cli.py:35-63, 184-328`), and `damage`, which the reference
+does not have (boolsi_amd/damage.py).
 
 Differences, all outside the hot path: results are kept in memory instead of a ZODB spill
 (`-d`, `-k` accepted and ignored); `-b` does not schedule anything (the GPU dequeues its own chunks),
@@ -270,6 +271,43 @@ def target(**kw):
                              comm=run.comm, listing=_listing(kw, cfg), samples=kw['samples'], seed=kw['seed'] or 0)
         if sims and run.comm.rank == 0:
             output_simulations(sims, cfg['node names'], run.out)
+    _guarded(kw, body)
+
+
+def _flips(ctx, param, value):
+    from .damage import parse_flips
+    try:
+        return parse_flips(value)
+    except ValueError:
+        raise click.BadParameter('a comma-separated list of positive integers, as in "1,2,4".')
+
+
+@cli.command(help='Measure how a difference of a few nodes between two sampled states spreads (Derrida curves).')
+@_common
+@click.option('-t', '--simulation-time', type=click.IntRange(min=1, max=65535), required=True,
+              help='(required) Number of time steps to follow every pair of states for.')
+@click.option('--samples', 'samples', type=click.IntRange(min=1),
+              help='(required) Number of sampled initial conditions; each gives one pair of states.')
+@_seed_option
+@click.option('--flips', 'flips', default='1', callback=_flips,
+              help='Numbers of nodes inverted in the second state of a pair, comma-separated. Defaults to 1.')
+@click.option('--histogram', 'histogram', is_flag=True,
+              help='Also write the distribution of distances per time step to damage_histogram.csv.')
+def damage(**kw):
+    _check_sampling(kw)
+    if kw['samples'] is None:
+        raise click.UsageError('damage needs --samples: pairs of states are sampled, never enumerated.')
+
+    def body(run):
+        from .damage import damage_master, output_damage
+        if run.comm.world > 1:
+            logging.getLogger().error('The damage command runs on one GPU; multi-rank runs are not supported.')
+            return
+        cfg = run.read_input(kw['simulation_time'], Mode.ATTRACT)
+        results = damage_master(run.open_engine(), cfg['origin simulation problem'], cfg['simulation problem variations'],
+                                cfg['incoming node lists'], cfg['truth tables'], kw['samples'], kw['seed'] or 0,
+                                kw['simulation_time'], kw['flips'], hist=kw['histogram'])
+        output_damage(results, kw['samples'], len(cfg['node names']), run.out, hist=kw['histogram'])
     _guarded(kw, body)
 
 

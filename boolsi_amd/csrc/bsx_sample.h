@@ -90,4 +90,33 @@ BSX_HD uint64_t sample_variant_of(uint64_t kb, uint32_t n_any, uint64_t j, uint6
     return sample_variant(sample_u(kb, n_any, (uint32_t)(j & 63u)), variant_count);
 }
 
+// ---- damage spreading (bsx_run_damage_sampled; include/bsx.h has the normative definition) ----
+// Sample j's partner y(0) is its x(0) with h distinct free nodes inverted (`free`: the ascending nodes the origin does not fix,
+// n_free of them).  Flip i = 0 .. h-1 draws
+//     D(j, i) = mix(kb(j >> 6) + G * (n_any + 65 + 64 i + lane))          lane = j & 63
+//     p       = (D(j, i) * (n_free - i)) >> 64
+// and then, for every position c chosen earlier in ascending order, p += 1 if p >= c: p is the position of the p-th free
+// node not chosen yet.  That is how it is computed here: `chosen` is a bit mask over the positions (bit c & 31 of word
+// c >> 5, the words `stride` apart so that a kernel can interleave the masks of its trajectories), and the p-th zero bit
+// is found word by word.  The arguments of D lie past those of A (1 .. n_any) and U (n_any + 1 .. n_any + 64).
+BSX_HD uint64_t damage_draw(uint64_t kb, uint32_t n_any, uint32_t lane, uint32_t i) {
+    return sample_mix(kb + kSampleG * ((uint64_t)n_any + 65u + 64ull * i + lane));
+}
+
+// Position of flip i (i positions are set in `chosen`, i < n_free) for the draw d; sets its bit and returns it.
+BSX_HD uint32_t damage_choose(uint64_t d, uint32_t n_free, uint32_t i, uint32_t* chosen, uint32_t stride) {
+    uint32_t p = (uint32_t)sample_mulhi(d, (uint64_t)(n_free - i));        // < n_free - i: the zero bits below n_free
+    const uint32_t n_words = (n_free + 31u) >> 5;
+    for (uint32_t w = 0; w < n_words; ++w) {
+        uint32_t open = ~chosen[w * stride];
+        const uint32_t zeros = (uint32_t)__builtin_popcount(open);
+        if (p >= zeros) { p -= zeros; continue; }
+        for (; p; --p) open &= open - 1u;                                   // drop the p lowest zero positions
+        const uint32_t bit = (uint32_t)__builtin_ctz(open);
+        chosen[w * stride] |= 1u << bit;
+        return 32u * w + bit;
+    }
+    return n_free;      // not reached: p < n_free - i
+}
+
 }  // namespace bsx

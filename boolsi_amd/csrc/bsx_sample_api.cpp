@@ -19,7 +19,7 @@
 using namespace bsx;
 
 // The WideHost a sampled call works on: the handle's own, or the second lowering (built here on first use).
-static int sample_host(bsx_handle h, WideHost** out) {
+int bsx::sample_host(bsx_handle h, WideHost** out) {
     if (h->wide) { *out = h->wide; return BSX_OK; }
     if (!h->sample_wide) {
         const SampleInputs& in = h->inputs;

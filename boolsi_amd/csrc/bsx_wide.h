@@ -112,6 +112,27 @@ inline uint32_t wide_profile_lds_words(uint32_t rows, uint32_t L, uint32_t n_fsl
     return 2 * rows * L + 2 * n_fslots * L + kWideThreads + 2 * L + 32 * L + 8;
 }
 
+// ---- damage spreading (k_wide_damage in bsx_wide.hip, bsx_run_damage_sampled; include/bsx.h has the definition) ----
+// A group of 32 * L samples holds two trajectories per sample: X (matrices 0 / 1) from the sampled source, Y (matrices
+// 2 / 3) = X with n_flips free nodes inverted.  Both step under the network part of `net` (origin fixed nodes are constant
+// rules; the space has no variations and no schedule, the host refuses the others).  d(t) of a sample is the column sum of
+// X ^ Y over all rows: 6-plane vertical counters over the rows a thread owns, combined across the slices through LDS.
+constexpr uint32_t kWideDamagePlanes = 6;       // rows a thread owns: at most kWideProfileRows = 36 < 2^6
+struct WideDamageParams {
+    WideParams net;                 // network part, origin, any_nodes / n_any, sample_k0, sample_first, count
+    uint32_t n_flips, n_steps;
+    uint32_t n_free, acc_lds;       // acc_lds: the (n_steps + 1) * 3 sums of a workgroup stay in LDS until it ends
+    const uint32_t* free_nodes;     // [n_free] ascending
+    unsigned long long* sums;       // [n_steps + 1][3] sum d, sum d^2, merged; zeroed by the host
+    unsigned long long* hist;       // nullable: [n_steps + 1][n_nodes + 1], zeroed by the host
+};
+// LDS words of k_wide_damage: four matrices, the (zero) fixed-variation masks, the planes of every thread, the block keys
+// of the columns, the sums of a step, the step's histogram (with hist) and the 64-bit accumulators (with acc_lds).
+inline uint32_t wide_damage_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslots, uint32_t n_nodes, bool hist, uint32_t acc_steps) {
+    return kWideBuffers * rows * L + 2 * n_fslots * L + kWideDamagePlanes * kWideThreads + 4 * L + 8 + (hist ? ((n_nodes + 2) & ~1u) : 0) +
+           6 * acc_steps;
+}
+
 // ---- attractor transitions (k_wide_trans / k_wide_trans_build in bsx_wide.hip, bsx_run_attractor_transitions_wide) ----
 // A group of 32 * L trajectories runs k_wide's attract phases (Brent in lock step, the mu pass, the key lap) with
 // T_p = 0 and the origin's fixed nodes only.  Two kinds of source:

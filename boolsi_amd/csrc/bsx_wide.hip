@@ -826,6 +826,175 @@ hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, c
 }
 
 // ------------------------------------------------------------------------------------------------
+// Damage spreading (bsx_run_damage_sampled; include/bsx.h has the definition, bsx_wide.h the layout).  Per lock step: two
+// wide_step calls, one vertical counter add per owned row of X ^ Y, the counters of the slices combined per sample
+// through LDS, and the step's three sums reduced per wave and then per workgroup.
+namespace {
+typedef Planes<1, (int)kWideDamagePlanes> DamagePlanes;
+}
+
+template <int K, bool KW>
+__global__ __launch_bounds__(kWideThreads) void k_wide_damage(const WideDamageParams Q) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
+    const WideParams& P = Q.net;
+    WideCtx X;
+    X.L = P.L;
+    X.tid = threadIdx.x;
+    X.c = X.tid & (P.L - 1);
+    X.slice = X.tid >> P.lshift;
+    X.r0 = X.slice * P.rows_ps;
+    X.r1 = X.r0 + P.rows_ps;
+    X.RL = P.rows * P.L;
+    const uint32_t L = P.L, c = X.c, RL = X.RL, G = 32 * L, tid = X.tid;
+    const uint32_t nslices = kWideThreads / L;
+    const uint32_t n_bins = P.n_nodes + 1;
+    const uint32_t n_acc = Q.acc_lds ? 3 * (Q.n_steps + 1) : 0;
+    const uint32_t mask_words = (Q.n_free + 31u) >> 5;             // of a sample's chosen positions; <= rows / 32
+    uint32_t* B[4] = {sm, sm + RL, sm + 2 * RL, sm + 3 * RL};       // X: 0 / 1, Y: 2 / 3
+    uint32_t* fmv = sm + 4 * RL;                    // [n_fslots][2][L]  all zero: no variations here
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(fmv + 2 * P.n_fslots * L);      // [n_steps + 1][3] (acc_lds)
+    uint32_t* pln = reinterpret_cast<uint32_t*>(acc + n_acc);       // [6][256]  every thread's planes
+    uint32_t* keys = pln + kWideDamagePlanes * kWideThreads;        // [L][4]    block keys of the columns
+    uint32_t* gacc = keys + 4 * L;                  // [2][4]            sums of step t in half t & 1
+    uint32_t* lh = gacc + 8;                        // [n_nodes + 1]     histogram of the step (hist)
+    unsigned long long steps_exec = 0;
+    for (uint32_t i = tid; i < 2 * P.n_fslots * L; i += kWideThreads) fmv[i] = 0;
+    for (uint32_t i = tid; i < n_acc; i += kWideThreads) acc[i] = 0ull;
+    if (Q.hist)
+        for (uint32_t i = tid; i < n_bins; i += kWideThreads) lh[i] = 0;
+    // sums[t][q] += v: in LDS until the workgroup ends (one owner per address and phase), else straight to HBM
+    auto add = [&](uint32_t t, uint32_t q, unsigned long long v) {
+        if (Q.acc_lds) acc[3 * t + q] += v;
+        else if (v) atomicAdd(&Q.sums[3 * (size_t)t + q], v);
+    };
+
+    const uint64_t n_groups = (P.count + G - 1) / G;
+    for (uint64_t group = blockIdx.x; group < n_groups; group += gridDim.x) {
+        const uint64_t base = group * G;
+        const uint32_t n_valid = (uint32_t)((P.count - base) < G ? (P.count - base) : G);
+        // ---- x(0) = y(0) = origin | 'any' words of the sampled source; the chosen-position masks (matrix 3) start empty
+        for (uint32_t i = tid; i < RL; i += kWideThreads) {
+            const uint32_t r = i >> P.lshift;
+            B[0][i] = B[2][i] = (r < P.n_nodes && ((P.origin[r >> 5] >> (r & 31u)) & 1u)) ? 0xFFFFFFFFu : 0u;
+        }
+        for (uint32_t i = tid; i < mask_words * G; i += kWideThreads) B[3][i] = 0;
+        if (tid < L) {
+            const SampleColumn sc = sample_column(P.sample_k0, P.sample_first + base + 32ull * tid);
+            keys[4 * tid + 0] = (uint32_t)sc.kb0; keys[4 * tid + 1] = (uint32_t)(sc.kb0 >> 32);
+            keys[4 * tid + 2] = (uint32_t)sc.kb1; keys[4 * tid + 3] = (uint32_t)(sc.kb1 >> 32);
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < P.n_any * L; i += kWideThreads) {
+            const uint32_t a = i >> P.lshift, cw = i & (L - 1);
+            const SampleColumn sc = wide_sample_column(keys, cw, P.sample_first + base + 32ull * cw);
+            const uint32_t n_bits = n_valid > 32 * cw ? (n_valid - 32 * cw < 32u ? n_valid - 32 * cw : 32u) : 0u;
+            const uint32_t word = sample_column_word(sc, a, n_bits);
+            B[0][P.any_nodes[a] * L + cw] = word;
+            B[2][P.any_nodes[a] * L + cw] = word;
+        }
+        __syncthreads();
+        // ---- y(0): n_flips distinct free nodes inverted per sample.  The positions chosen so far are a bit mask in LDS
+        // (word w of sample k at B[3][w * G + k]), not a list in registers.
+        for (uint32_t k = tid; k < n_valid; k += kWideThreads) {
+            const uint32_t cw = k >> 5, bit = 1u << (k & 31u);
+            const SampleColumn sc = wide_sample_column(keys, cw, P.sample_first + base + 32ull * cw);
+            const uint64_t kb = sample_column_key(sc, k & 31u);
+            const uint32_t lane = sample_column_lane(sc, k & 31u);
+            for (uint32_t i = 0; i < Q.n_flips; ++i) {
+                const uint32_t p = damage_choose(damage_draw(kb, P.n_any, lane, i), Q.n_free, i, B[3] + k, G);
+                if (p < Q.n_free) atomicXor(&B[2][Q.free_nodes[p] * L + cw], bit);
+            }
+        }
+        __syncthreads();
+        uint32_t *xc = B[0], *xn = B[1], *yc = B[2], *yn = B[3];
+        uint32_t group_steps = 0;
+        for (uint32_t t = 0;; ++t) {
+            uint32_t* ga = gacc + 4 * (t & 1u);
+            if (tid < 4) ga[tid] = 0;               // (last read two steps ago, or in the group before)
+            // ---- d(t): column sums of X ^ Y over the owned rows (written by this thread), then over the slices
+            DamagePlanes pl;
+            planes_clear(pl);
+            for (uint32_t r = X.r0; r < X.r1; ++r) {
+                const uint32_t s[1] = {xc[r * L + c] ^ yc[r * L + c]};
+                planes_add(pl, s);
+            }
+#pragma unroll
+            for (int j = 0; j < (int)kWideDamagePlanes; ++j) pln[j * kWideThreads + tid] = pl.p[j][0];
+            __syncthreads();
+            uint32_t sd = 0, sd2 = 0, mg = 0;       // per group and step: sum d <= 2^21, sum d^2 <= 2^31
+            for (uint32_t k = tid; k < n_valid; k += kWideThreads) {
+                const uint32_t cw = k >> 5, b = k & 31u;
+                uint32_t d = 0;
+                for (uint32_t s = 0; s < nslices; ++s) {
+                    uint32_t cnt = 0;
+#pragma unroll
+                    for (int j = 0; j < (int)kWideDamagePlanes; ++j) cnt |= ((pln[j * kWideThreads + s * L + cw] >> b) & 1u) << j;
+                    d += cnt;
+                }
+                sd += d; sd2 += d * d; mg += d == 0 ? 1u : 0u;
+                if (Q.hist) atomicAdd(&lh[d], 1u);
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                sd += __shfl_xor(sd, off); sd2 += __shfl_xor(sd2, off); mg += __shfl_xor(mg, off);
+            }
+            if ((tid & 63u) == 0) { atomicAdd(&ga[0], sd); atomicAdd(&ga[1], sd2); atomicAdd(&ga[2], mg); }
+            const bool last = t == Q.n_steps;
+            if (!last) {
+                wide_step<K, KW>(P, X, xc, xn, fmv, 0xFFFFFFFFu);
+                wide_step<K, KW>(P, X, yc, yn, fmv, 0xFFFFFFFFu);
+                ++group_steps;
+            }
+            __syncthreads();
+            if (tid < 3) add(t, tid, ga[tid]);
+            if (Q.hist) {
+                for (uint32_t i = tid; i < n_bins; i += kWideThreads) {
+                    const uint32_t v = lh[i];
+                    if (v) { atomicAdd(&Q.hist[(size_t)t * n_bins + i], (unsigned long long)v); lh[i] = 0; }
+                }
+            }
+            if (last) break;
+            if (ga[2] == n_valid) {
+                // every pair of the group has merged, and merged pairs stay merged: d = 0 from here on
+                for (uint32_t t2 = t + 1 + tid; t2 <= Q.n_steps; t2 += kWideThreads) {
+                    add(t2, 2, n_valid);
+                    if (Q.hist) atomicAdd(&Q.hist[(size_t)t2 * n_bins], (unsigned long long)n_valid);
+                }
+                break;
+            }
+            uint32_t* s = xc; xc = xn; xn = s;
+            s = yc; yc = yn; yn = s;
+        }
+        steps_exec += 2ull * group_steps * n_valid;
+        __syncthreads();
+    }
+    for (uint32_t i = tid; i < n_acc; i += kWideThreads)
+        if (acc[i]) atomicAdd(&Q.sums[i], acc[i]);
+    if (tid == 0 && steps_exec) atomicAdd(&P.ctr[1], steps_exec);
+}
+
+template <int K>
+static hipError_t launch_wide_damage_k(dim3 grid, size_t shmem, hipStream_t st, const WideDamageParams& Q) {
+    const void* fn = Q.net.wdesc ? (const void*)k_wide_damage<K, true> : (const void*)k_wide_damage<K, false>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return e;
+    void* args[] = {const_cast<WideDamageParams*>(&Q)};
+    return hipLaunchKernel(fn, grid, dim3(kWideThreads), args, shmem, st);
+}
+
+hipError_t launch_wide_damage(int k, dim3 grid, size_t shmem, hipStream_t st, const WideDamageParams& Q) {
+    switch (k) {
+        case 1: return launch_wide_damage_k<1>(grid, shmem, st, Q);
+        case 2: return launch_wide_damage_k<2>(grid, shmem, st, Q);
+        case 3: return launch_wide_damage_k<3>(grid, shmem, st, Q);
+        case 4: return launch_wide_damage_k<4>(grid, shmem, st, Q);
+        case 5: return launch_wide_damage_k<5>(grid, shmem, st, Q);
+        case 6: return launch_wide_damage_k<6>(grid, shmem, st, Q);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Attractor transitions (bsx_run_attractor_transitions_wide; bsx_wide.h has the stages, bsx_wtrans.h the lookup and
 // the classification).  The walk is k_wide's attract branch with T_p = 0, no schedule and no variations.
 namespace {

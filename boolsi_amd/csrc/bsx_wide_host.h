@@ -14,6 +14,7 @@ hipError_t launch_wide(int k, dim3 grid, size_t shmem, hipStream_t st, const Wid
 hipError_t launch_wide_sampled(int k, dim3 grid, size_t shmem, hipStream_t st, const WideParams& P);
 hipError_t launch_sample_problems(const WideSampleListParams& Q, hipStream_t st);
 hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, const WideProfileParams& Q);
+hipError_t launch_wide_damage(int k, dim3 grid, size_t shmem, hipStream_t st, const WideDamageParams& Q);
 hipError_t launch_wide_trans(int k, dim3 grid, size_t shmem, hipStream_t st, const WideTransParams& Q);
 hipError_t launch_wide_trans_build(const WideTransParams& Q, hipStream_t st);
 hipError_t launch_wide_reduce_attract(const uint32_t* info, const uint64_t* keys, uint64_t m, uint32_t w64, WideSlot* table,
@@ -110,6 +111,8 @@ int wide_sim(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, uint64_
 int wide_target_summary(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, const uint64_t* mask_words,
                         const uint64_t* code_words, uint64_t* hist, uint32_t hist_bins, bsx_hit* hits, uint64_t cap,
                         uint64_t* n_hits, uint64_t* n_listed, bsx_stats* stats, double t_call);
+// bsx_sample_api.cpp: the WideHost a call over samples works on (bsx_damage_api.cpp takes it from there too)
+int sample_host(bsx_handle h, WideHost** out);
 // bsx_wide_attract_api.cpp: the two legs of an attract call over `count` problems in launches of `chunk`, behind
 // bsx_run_attract_wide and bsx_run_attract_sampled.
 int attract_wide_device(bsx_handle h, WideHost& W, WideSource& src, uint64_t count, uint64_t chunk, uint64_t max_len,

@@ -426,6 +426,18 @@ class Engine:
                                                        ptr(dig) if digest else None, C.byref(st)))
         return traj, fin, dig, st.as_dict()
 
+    def damage_sampled(self, seed, first, count, n_flips, n_steps, hist=False):
+        """bsx_run_damage_sampled: damage spreading over samples [first, first + count) of `seed` (include/bsx.h has the
+        definition) -> (sum_d, sum_d2, n_merged: uint64 (n_steps + 1,); hist: uint64 (n_steps + 1, n + 1) or None; stats)."""
+        n_t = int(n_steps) + 1
+        sum_d, sum_d2, merged = (np.zeros(n_t, np.uint64) for _ in range(3))
+        cells = np.zeros((n_t, self.net.n_nodes + 1), np.uint64) if hist else None
+        st = Stats()
+        self._check(self._lib.bsx_run_damage_sampled(self._h, int(seed), int(first), int(count), int(n_flips), int(n_steps),
+                                                     ptr(sum_d), ptr(sum_d2), ptr(merged), ptr(cells) if hist else None,
+                                                     C.byref(st)))
+        return sum_d, sum_d2, merged, cells, st.as_dict()
+
     def trajectories_sampled(self, seed, samples, t_len):
         """States s(0..t_len[q]) of samples samples[q] of `seed` -> list of (t_len[q] + 1, W) arrays."""
         W = self.net.n_words

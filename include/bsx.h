@@ -294,6 +294,40 @@ int  bsx_run_simulate_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample
 int  bsx_run_trajectories_sampled(bsx_handle h, uint64_t seed, const uint64_t* samples, const uint64_t* t_len, uint64_t n,
                                   uint64_t* out, const uint64_t* out_offsets, bsx_stats* stats);
 
+/* ---- damage spreading over sampled pairs of states: Derrida curves (no reference analogue) ----
+ * How does a difference of n_flips nodes between two states grow or die over n_steps updates?  This definition is
+ * NORMATIVE and implemented in boolsi_amd/csrc/bsx_sample.h; the notation is that of the sampled source above.  For
+ * sample j of `seed`, kb = kb(j >> 6), lane = j & 63, h = n_flips, T = n_steps:
+ *
+ *   - x(0) is the sample's initial state as bsx_sample_problems gives it: 'any' nodes from A(b, a), the others from the
+ *     origin;
+ *   - free = the ascending list of the nodes that the origin does not fix, n_free of them;
+ *   - for i = 0 .. h-1:   D(j, i) = mix(kb + G * (n_any + 65 + 64 i + lane))      (arguments past those of A and U)
+ *                          p = (D(j, i) * (n_free - i)) >> 64
+ *                          for every position c chosen earlier, in ascending order of c: if p >= c then p += 1
+ *                          position p is chosen;
+ *   - y(0) = x(0) with free[p] inverted for the h chosen positions (distinct by construction: d(0) = h exactly);
+ *   - x(t+1) = F(x(t)), y(t+1) = F(y(t)) under the network's rules and the origin's fixed nodes only;
+ *   - d_j(t) = popcount(x(t) ^ y(t)) for t = 0 .. T.
+ *
+ * Over samples [first_sample, first_sample + n_samples):  sum_d[t] = sum of d_j(t),  sum_d2[t] = sum of d_j(t)^2,
+ * n_merged[t] = samples with d_j(t) == 0,  hist[t * (n_nodes + 1) + k] (nullable) = samples with d_j(t) == k.  A pure
+ * function of (seed, first_sample, n_samples, n_flips, n_steps); disjoint sample ranges add up to their union.  Works on
+ * handles of both families (the second lowering of bsx_run_attract_sampled).  The arrays are written only by a call that
+ * succeeds; n_samples == 0 is BSX_OK with zeros written.  stats: problems = n_samples, state_steps = 2 * n_samples *
+ * n_steps, executed_steps = the updates that ran (a group whose every pair has merged stops stepping: merged pairs stay
+ * merged).
+ *
+ * Checked before anything is launched:  BSX_ERR_STATE without a network or a problem space;  BSX_ERR_INVALID if
+ * first_sample + n_samples wraps, n_flips is 0, above n_free or above BSX_DAMAGE_MAX_FLIPS, or a required array is NULL;
+ * BSX_ERR_RANGE_TOO_LARGE for more than 2^40 samples (the sums stay below 2^60);  BSX_ERR_UNSUPPORTED for a space with
+ * fixed-node variations, perturbation variations or an origin perturbation schedule (the text says which: never a silent
+ * reinterpretation), for n_steps > 65535, and for hist with more than 2^24 cells. */
+#define BSX_DAMAGE_MAX_FLIPS 64
+int  bsx_run_damage_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample, uint64_t n_samples,
+                            uint32_t n_flips, uint32_t n_steps,
+                            uint64_t* sum_d, uint64_t* sum_d2, uint64_t* n_merged, uint64_t* hist, bsx_stats* stats);
+
 /* target (target.py:109-133): hits in ascending offset order into hits[0..*n_hits); mask/code are W words
  * (target node set / target substate code, input.py:580-661). */
 int  bsx_run_target(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t,
