@@ -25,7 +25,7 @@ EXPORTS = (
     'bsx_set_network', 'bsx_set_problem_space', 'bsx_run_attract', 'bsx_run_attract2', 'bsx_run_attract_wide', 'bsx_run_attract_fgraph', 'bsx_run_target',
     'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_run_attractor_profile', 'bsx_run_node_correlations', 'bsx_run_attractor_transitions', 'bsx_run_attractor_transitions_wide',
     'bsx_run_attract_sampled', 'bsx_sample_problems',
-    'bsx_run_target_sampled', 'bsx_run_simulate_sampled', 'bsx_run_trajectories_sampled', 'bsx_run_damage_sampled',
+    'bsx_run_target_sampled', 'bsx_run_simulate_sampled', 'bsx_run_trajectories_sampled', 'bsx_run_damage_sampled', 'bsx_run_screen_sampled',
     'bsx_synchronize',
     'bsx_comm_unique_id', 'bsx_comm_init', 'bsx_comm_allgather', 'bsx_comm_destroy',
 )
@@ -35,6 +35,8 @@ CORR_MAX_CELLS = 1 << 31    # BSX_CORR_MAX_CELLS
 TRANS_MAX_STATES = 1 << 28  # BSX_TRANS_MAX_STATES
 TRANS_OUTSIDE = 0xFFFFFFFE  # BSX_TRANS_OUTSIDE
 TRANS_UNRESOLVED = 0xFFFFFFFF   # BSX_TRANS_UNRESOLVED
+SCREEN_MAX_NODES = 4        # BSX_SCREEN_MAX_NODES
+SCREEN_MAX_MUTANTS = 1 << 20    # BSX_SCREEN_MAX_MUTANTS
 
 
 class EngineUnavailable(RuntimeError):
@@ -104,6 +106,8 @@ ATTR_REC2 = np.dtype([('key', '<u8', (MAX_WORDS,)), ('length', '<u8'), ('count',
 # bsx_attr_rec2w: ATTR_REC2 with BSX_MAX_STATE_WORDS key words (bsx_run_attract_wide)
 ATTR_REC2W = np.dtype([('key', '<u8', (MAX_STATE_WORDS,)), ('length', '<u8'), ('count', '<u8', (2,)),
                        ('sum_l', '<u8', (3,)), ('sum_l2', '<u8', (4,))])
+# bsx_screen_rec (bsx_run_screen_sampled): the mutant, then its ATTR_REC2W
+SCREEN_REC = np.dtype([('mutant', '<u8'), ('rec', ATTR_REC2W)])
 PROBLEM_REC = np.dtype([('key', '<u8', (MAX_WORDS,)), ('length', '<u8'), ('trajectory_l', '<u8'),
                         ('found', '<u4'), ('pad', '<u4')])
 HIT = np.dtype([('offset', '<u8'), ('t', '<u8')])
@@ -155,6 +159,7 @@ def load():
     lib.bsx_run_simulate_sampled.argtypes = [vp, u64, u64, u64, u64, vp, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_trajectories_sampled.argtypes = [vp, u64, vp, vp, u64, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_damage_sampled.argtypes = [vp, u64, u64, u64, u32, u32, vp, vp, vp, vp, C.POINTER(Stats)]
+    lib.bsx_run_screen_sampled.argtypes = [vp, u64, u64, u64, vp, vp, u32, u64, u64, vp, u64, C.POINTER(u64), vp, C.POINTER(Stats2)]
     lib.bsx_run_attract_fgraph.argtypes = [vp, C.POINTER(Index), u64, u64, u64, vp, u32, C.POINTER(u32),
                                            C.POINTER(u64), C.POINTER(Stats)]
     lib.bsx_run_target.argtypes = [vp, C.POINTER(Index), u64, u64, vp, vp, vp, u64, C.POINTER(u64),

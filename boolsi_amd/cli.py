@@ -1,7 +1,7 @@
 """
 Command line: `python -m boolsi_amd simulate|attract|target FILE [options]`, same commands and
-option names as the reference's `boolsi` script (`boolsi/cli.py:35-63, 184-328`), and `damage`, which the reference
-does not have (boolsi_amd/damage.py).
+option names as the reference's `boolsi` script (`boolsi/cli.py:35-63, 184-328`), and `damage` and `screen`, which the
+reference does not have (boolsi_amd/damage.py, boolsi_amd/screen.py).
 
 Differences, all outside the hot path: results are kept in memory instead of a ZODB spill
 (`-d`, `-k` accepted and ignored); `-b` does not schedule anything (the GPU dequeues its own chunks),
@@ -308,6 +308,68 @@ def damage(**kw):
                                 cfg['incoming node lists'], cfg['truth tables'], kw['samples'], kw['seed'] or 0,
                                 kw['simulation_time'], kw['flips'], hist=kw['histogram'])
         output_damage(results, kw['samples'], len(cfg['node names']), run.out, hist=kw['histogram'])
+    _guarded(kw, body)
+
+
+def _values(ctx, param, value):
+    from .screen import parse_values
+    try:
+        return parse_values(value)
+    except ValueError:
+        raise click.BadParameter('a comma-separated list of distinct states 0 / 1, as in "0,1".')
+
+
+def _screen_mutants(kw):
+    """The mutant list of `screen`, from the input's node names and fixed nodes alone: a usage error where it cannot be
+    built.  An input that does not parse is left to the run itself, which reports it the usual way."""
+    from .input import parse_input
+    from .screen import ScreenUsageError, build_mutants
+    logging.disable(logging.CRITICAL)
+    try:
+        cfg = parse_input(kw['input_file'], kw['max_simulation_time'] or inf, Mode.ATTRACT)
+    except Exception:   # noqa: BLE001
+        return None
+    finally:
+        logging.disable(logging.NOTSET)
+    names = None if kw['nodes'] is None else [name.strip() for name in kw['nodes'].split(',')]
+    try:
+        return build_mutants(cfg['node names'], cfg['origin simulation problem'][1], names, kw['values'], kw['pairs'])
+    except ScreenUsageError as e:
+        raise click.UsageError(str(e))
+
+
+@cli.command(help='Screen knockouts and overexpressions: the attractors of every mutant over the same sampled initial '
+                  'conditions, against the wild type.')
+@_common
+@click.option('-t', '--max-simulation-time', type=click.IntRange(min=1),
+              help='Maximum simulation time. If set, simulation stops after this time step even if '
+                   'attractor was not found.')
+@click.option('-a', '--max-attractor-length', type=click.IntRange(min=1),
+              help='Maximum length of attractor to look for. If set, attractors longer than this value are discarded.')
+@click.option('--samples', 'samples', type=click.IntRange(min=1),
+              help='(required) Number of sampled initial conditions; every mutant runs on the same ones.')
+@_seed_option
+@click.option('--nodes', 'nodes', default=None,
+              help='Names of the nodes to screen, comma-separated. Defaults to every node the input does not fix.')
+@click.option('--values', 'values', default='0,1', callback=_values,
+              help='States to hold a node at: 0 (knockout), 1 (overexpression) or both, comma-separated. Defaults to 0,1.')
+@click.option('--pairs', 'pairs', is_flag=True, help='Also screen every pair of the listed nodes.')
+def screen(**kw):
+    _check_sampling(kw)
+    if kw['samples'] is None:
+        raise click.UsageError('screen needs --samples: mutants are compared over sampled initial conditions, never enumerated.')
+    mutants = _screen_mutants(kw)
+
+    def body(run):
+        from .screen import output_screen, screen_master
+        if run.comm.world > 1:
+            logging.getLogger().error('The screen command runs on one GPU; multi-rank runs are not supported.')
+            return
+        cfg = run.read_input(kw['max_simulation_time'] or inf, Mode.ATTRACT)
+        tables, none = screen_master(run.open_engine(), cfg['origin simulation problem'], cfg['simulation problem variations'],
+                                     cfg['incoming node lists'], cfg['truth tables'], kw['samples'], kw['seed'] or 0, mutants,
+                                     kw['max_simulation_time'] or inf, kw['max_attractor_length'] or inf)
+        output_screen(tables, none, mutants, cfg['node names'], kw['samples'], run.out)
     _guarded(kw, body)
 
 

@@ -173,6 +173,28 @@ inline uint32_t wide_trans_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslot
     return kWideBuffers * rows * L + 2 * n_fslots * L + 2 * kWideThreads + 8 * L + 4 * 32 * L + 8;
 }
 
+// ---- mutant screens over samples (k_wide_screen in bsx_wide.hip, bsx_run_screen_sampled; include/bsx.h has the
+// definition, bsx_screen.h the layout) ----
+// The work items of a launch are (mutant, group) pairs p = p0 + i, i < n_pairs: group p % g_per of mutant p / g_per, its
+// trajectories the samples first_sample + 32 L * group + k of the sampled source.  A workgroup runs k_wide's attract
+// phases with T_p = 0 (as k_wide_trans) and, after every step, rewrites the rows of its mutant's nodes under the step's
+// freeze mask.  Record (i * 32 L + k) of the launch goes to info / keys of `net`; records behind the end of a ragged
+// group are not written (the reduction knows a record's pair, and so its validity, from its position).
+// `net` carries the network part, origin, any_nodes / n_any, sample_k0, max_t / cap_inf / step_limit, max_len, info /
+// keys, x0 and ctr; the space has no variations and no schedule (the host refuses the others).
+struct WideScreenParams {
+    WideParams net;
+    uint64_t first_sample, n_samples;
+    uint64_t p0, n_pairs, g_per;
+    const uint32_t* mut_offsets;    // [n_mutants + 1]
+    const uint32_t* mut_nodes;      // [mut_offsets[n_mutants]][2] node, value (bsx_fixed)
+};
+// LDS words of k_wide_screen: k_wide's layout without perturbation variations and without T_p (never more than
+// wide_lds_words gives for the L that wide_lower_space chose)
+inline uint32_t wide_screen_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslots) {
+    return kWideBuffers * rows * L + 2 * n_fslots * L + 2 * kWideThreads + 8 * L + 3 * 32 * L + 8;
+}
+
 // ---- device-side reduction of the kernel's per-problem records (bsx_wide_reduce.hip) ----
 // Attract: an open-addressing HBM table keyed by the whole w64-word key, linear probing.
 // Widths of the sums, for at most 2^64 - 1 problems per call (bsx_run_attract_wide refuses more) and
@@ -208,6 +230,21 @@ constexpr uint32_t kWideReduceLdsSlots = 128;   // entries of that LDS table
 constexpr uint32_t kWideReduceMinSlots = 1024;  // smallest HBM table
 // Largest min(cap, count) reduced on the device: 2^21 slots of 184 bytes and 2^20 records of 208 bytes, 0.6 GB.
 constexpr uint64_t kWideReduceMaxCap = 1ull << 20;
+// The screen's table slot and drained record (bsx_screen_reduce.hip): WideSlot / WideAttrRec with the mutant in the key.
+struct ScreenSlot {
+    uint32_t state;             // 0 empty, 1 key being written, 2 ready
+    uint32_t length;
+    unsigned long long mutant;
+    unsigned long long count;
+    unsigned long long sum_l[2];
+    unsigned long long sum_l2[3];
+    unsigned long long key[kWideMaxW32 / 2];    // words past w64 stay 0
+};
+struct ScreenRec {              // the layout of bsx_screen_rec (include/bsx.h)
+    uint64_t mutant;
+    WideAttrRec rec;
+};
+constexpr uint32_t kScreenInlineRecs = 256;     // records that come back with the header in the call's one copy
 
 // LDS words of a workgroup for L columns (bsx_wide.hip lays them out in this order).
 inline uint32_t wide_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslots, uint32_t n_pv) {

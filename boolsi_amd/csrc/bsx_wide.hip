@@ -11,12 +11,14 @@
 //     row down (per-slice lt / eq masks, combined across slices from the top).
 // k_wide<K, KW, true> (attract) and k_wide<K, KW, true, MODE> (target, simulate) run over samples of a seed instead of
 // consecutive problem indices (bsx_sample.h): the same body, with the group's set-up and the one branch an instantiation
-// carries chosen at compile time.
+// carries chosen at compile time.  k_wide_screen (at the end of the file) runs the attract phases per (mutant, group)
+// pair of a knockout / overexpression screen over samples.
 #include <hip/hip_runtime.h>
 
 #include "bsx_device.h"
 #include "bsx_planes.h"
 #include "bsx_sample.h"
+#include "bsx_screen.h"
 #include "bsx_trans.h"
 #include "bsx_wide.h"
 #include "bsx_wtrans.h"
@@ -1352,6 +1354,279 @@ hipError_t launch_wide_trans_build(const WideTransParams& Q, hipStream_t st) {
     const uint64_t blocks = (Q.n_rows + 255) / 256;
     hipLaunchKernelGGL(k_wide_trans_build, dim3((uint32_t)blocks), dim3(256), 0, st, Q);
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mutant screens over samples (bsx_run_screen_sampled; include/bsx.h has the definition, bsx_wide.h / bsx_screen.h the
+// layout).  A workgroup's work items are (mutant, group) pairs: the sampled source's set-up, then k_wide's attract phases
+// with T_p = 0 (the body of k_wide_trans's row stage, copied: a shared body changed the figures of the older kernels), and
+// behind every wide_step the override of the mutant's rows.
+namespace {
+
+// The mutant of a workgroup's pair: up to BSX_SCREEN_MAX_NODES (row, word) pairs, uniform over the workgroup; an unused
+// entry has row kWideNone, which no thread owns.
+struct WideMutant {
+    uint32_t row[BSX_SCREEN_MAX_NODES];
+    uint32_t word[BSX_SCREEN_MAX_NODES];        // all ones for value 1, 0 for value 0
+};
+
+// Behind wide_step(cur -> nxt, act): the thread that owns row v of its column rewrites the word it has just written
+// itself (no barrier), under the same freeze mask: a frozen bit keeps its value, a live one has the mutant's.
+__device__ __forceinline__ void wide_screen_override(const WideMutant& M, const WideCtx& X, const uint32_t* cur, uint32_t* nxt, uint32_t act) {
+#pragma unroll
+    for (int i = 0; i < BSX_SCREEN_MAX_NODES; ++i) {
+        const uint32_t v = M.row[i];
+        if (v >= X.r0 && v < X.r1) nxt[v * X.L + X.c] = wbfi(act, M.word[i], cur[v * X.L + X.c]);
+    }
+}
+
+}  // namespace
+
+template <int K, bool KW>
+__global__ __launch_bounds__(kWideThreads) void k_wide_screen(const WideScreenParams Q) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
+    const WideParams& P = Q.net;
+    WideCtx X;
+    X.L = P.L;
+    X.tid = threadIdx.x;
+    X.c = X.tid & (P.L - 1);
+    X.slice = X.tid >> P.lshift;
+    X.r0 = X.slice * P.rows_ps;
+    X.r1 = X.r0 + P.rows_ps;
+    X.RL = P.rows * P.L;
+    const uint32_t L = P.L, c = X.c, RL = X.RL, G = 32 * L, tid = X.tid;
+    const uint32_t nslices = kWideThreads / L;
+    uint32_t* B[4] = {sm, sm + RL, sm + 2 * RL, sm + 3 * RL};
+    uint32_t* fmv = sm + 4 * RL;                    // [n_fslots][2][L]  all zero: no variations here
+    uint32_t* red = fmv + 2 * P.n_fslots * L;       // [2][256]          per-thread partials
+    uint32_t* col = red + 2 * kWideThreads;         // [8][L]            per-column masks (set-up: the columns' block keys)
+    uint32_t* lam = col + 8 * L;                    // [G] lambda
+    uint32_t* mua = lam + G;                        // [G] mu
+    uint32_t* sta = mua + G;                        // [G] state of the trajectory's search
+    uint32_t* misc = sta + G;                       // [8]
+    enum : uint32_t { ST_ACTIVE = 0, ST_CAND = 1, ST_FOUND = 2, ST_NONE = 3, ST_INVALID = 4 };
+    unsigned long long steps_ref = 0, steps_exec = 0, limit_hits = 0;
+    for (uint32_t i = tid; i < 2 * P.n_fslots * L; i += kWideThreads) fmv[i] = 0;
+    // found iff mu + lambda <= max_t (T_p = 0); a max_t at or beyond a quarter of the step limit counts as unbounded (k_wide)
+    const uint64_t cap = (P.cap_inf || P.max_t >= P.step_limit / 4) ? ~0ull : P.max_t;
+
+    for (uint64_t pi = blockIdx.x; pi < Q.n_pairs; pi += gridDim.x) {
+        const ScreenPair pair = screen_pair_of(Q.p0 + pi, Q.g_per, Q.n_samples, G);
+        const uint32_t n_valid = pair.n_valid;
+        const uint64_t j_first = Q.first_sample + pair.group * G;           // the group's first sample
+        const uint64_t rec0 = pi * G;                                       // its first record of this launch
+        // ---- the pair's mutant (uniform: scalar loads)
+        WideMutant M;
+        {
+            const uint32_t m0 = Q.mut_offsets[pair.mutant], m1 = Q.mut_offsets[pair.mutant + 1];
+#pragma unroll
+            for (int i = 0; i < BSX_SCREEN_MAX_NODES; ++i) {
+                const bool have = m0 + (uint32_t)i < m1;
+                M.row[i] = have ? Q.mut_nodes[2 * (m0 + i)] : kWideNone;
+                M.word[i] = have && Q.mut_nodes[2 * (m0 + i) + 1] ? 0xFFFFFFFFu : 0u;
+            }
+        }
+        // ---- s(0) = origin | 'any' words of the sampled source, whatever the mutant is
+        for (uint32_t i = tid; i < RL; i += kWideThreads) {
+            const uint32_t r = i >> P.lshift;
+            B[0][i] = (r < P.n_nodes && ((P.origin[r >> 5] >> (r & 31u)) & 1u)) ? 0xFFFFFFFFu : 0u;
+        }
+        if (tid < 8) misc[tid] = 0;
+        if (tid < L) {
+            const SampleColumn sc = sample_column(P.sample_k0, j_first + 32ull * tid);
+            col[4 * tid + 0] = (uint32_t)sc.kb0; col[4 * tid + 1] = (uint32_t)(sc.kb0 >> 32);
+            col[4 * tid + 2] = (uint32_t)sc.kb1; col[4 * tid + 3] = (uint32_t)(sc.kb1 >> 32);
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < P.n_any * L; i += kWideThreads) {
+            const uint32_t a = i >> P.lshift, cw = i & (L - 1);
+            const SampleColumn sc = wide_sample_column(col, cw, j_first + 32ull * cw);
+            const uint32_t n_bits = n_valid > 32 * cw ? (n_valid - 32 * cw < 32u ? n_valid - 32 * cw : 32u) : 0u;
+            B[0][P.any_nodes[a] * L + cw] = sample_column_word(sc, a, n_bits);
+        }
+        for (uint32_t k = tid; k < G; k += kWideThreads) {
+            sta[k] = k < n_valid ? ST_ACTIVE : ST_INVALID;
+            lam[k] = 0; mua[k] = 0;
+        }
+        __syncthreads();
+        uint32_t* cur = B[0];
+        uint32_t* nxt = B[1];
+        uint64_t group_steps = 0;
+        uint32_t* x0 = P.x0 + (size_t)blockIdx.x * RL;
+        for (uint32_t r = X.r0; r < X.r1; ++r) x0[r * L + c] = cur[r * L + c];
+        // ---- Brent's detector in lock step; the tortoise lives in B[2]
+        {
+            uint32_t* T = B[2];
+            for (uint32_t r = X.r0; r < X.r1; ++r) T[r * L + c] = cur[r * L + c];
+            uint64_t tau = 0, power = 1, lamc = 0;
+            for (;;) {
+                bool left = false;
+                if (tid < L)
+                    for (uint32_t b = 0; b < 32; ++b) left = left || sta[32 * tid + b] == ST_ACTIVE;
+                if (!__syncthreads_or(left)) break;
+                wide_step<K, KW>(P, X, cur, nxt, fmv, 0xFFFFFFFFu);
+                wide_screen_override(M, X, cur, nxt, 0xFFFFFFFFu);
+                ++tau; ++lamc; ++group_steps;
+                const bool tele = lamc == power;
+                uint32_t diff = 0;
+                for (uint32_t r = X.r0; r < X.r1; ++r) {          // (own rows only: no barrier between write and read)
+                    const uint32_t v = nxt[r * L + c];
+                    diff |= v ^ T[r * L + c];
+                    if (tele) T[r * L + c] = v;
+                }
+                red[tid] = diff;
+                __syncthreads();
+                if (tid < L) {
+                    uint32_t df = 0;
+                    for (uint32_t s = 0; s < nslices; ++s) df |= red[s * L + tid];
+                    for (uint32_t b = 0; b < 32; ++b) {
+                        const uint32_t k = 32 * tid + b;
+                        if (sta[k] != ST_ACTIVE) continue;
+                        if (!((df >> b) & 1u)) {
+                            lam[k] = (uint32_t)lamc;
+                            sta[k] = (uint64_t)lamc > cap ? ST_NONE : ST_CAND;
+                            if (sta[k] == ST_NONE) steps_ref += P.max_t;
+                        } else if (cap == ~0ull ? tau >= P.step_limit : tau >= 3 * cap + 2) {
+                            sta[k] = ST_NONE;
+                            if (cap == ~0ull) ++limit_hits;
+                            else steps_ref += P.max_t;
+                        }
+                    }
+                }
+                if (tele) { power <<= 1; lamc = 0; }
+                uint32_t* s = cur; cur = nxt; nxt = s;
+            }
+        }
+        // ---- mu: y = s(lambda) (bit b frozen after lambda_b steps) in B[0] / B[1], x = s(0) in B[2] / B[3]
+        if (tid == 0) misc[2] = 0;
+        __syncthreads();
+        if (tid < L)
+            for (uint32_t b = 0; b < 32; ++b)
+                if (sta[32 * tid + b] == ST_CAND) atomicMax(&misc[2], lam[32 * tid + b]);
+        __syncthreads();
+        const uint32_t lam_max = misc[2];
+        uint32_t* mn = B[2];
+        if (lam_max) {
+            uint32_t* ya = B[0]; uint32_t* yb = B[1];
+            uint32_t* xa = B[2]; uint32_t* xb = B[3];
+            for (uint32_t r = X.r0; r < X.r1; ++r) { ya[r * L + c] = x0[r * L + c]; xa[r * L + c] = x0[r * L + c]; }
+            for (uint32_t m = 0; m < lam_max; ++m) {
+                if (tid < L) {
+                    uint32_t act = 0;
+                    for (uint32_t b = 0; b < 32; ++b) act |= (m < lam[32 * tid + b] ? 1u : 0u) << b;
+                    col[tid] = act;
+                }
+                __syncthreads();
+                wide_step<K, KW>(P, X, ya, yb, fmv, col[c]);
+                wide_screen_override(M, X, ya, yb, col[c]);
+                __syncthreads();
+                uint32_t* s = ya; ya = yb; yb = s;
+                ++group_steps;
+            }
+            for (uint64_t m = 0;; ++m) {
+                uint32_t diff = 0;
+                for (uint32_t r = X.r0; r < X.r1; ++r) diff |= ya[r * L + c] ^ xa[r * L + c];
+                red[tid] = diff;
+                __syncthreads();
+                bool left = false;
+                if (tid < L) {
+                    uint32_t df = 0;
+                    for (uint32_t s = 0; s < nslices; ++s) df |= red[s * L + tid];
+                    for (uint32_t b = 0; b < 32; ++b) {
+                        const uint32_t k = 32 * tid + b;
+                        if (sta[k] != ST_CAND) continue;
+                        if (!((df >> b) & 1u)) {
+                            mua[k] = (uint32_t)m;
+                            sta[k] = ST_FOUND;
+                            steps_ref += m + lam[k];
+                        } else if (m + 1 + lam[k] > cap) {
+                            sta[k] = ST_NONE;
+                            steps_ref += P.max_t;
+                        } else {
+                            left = true;
+                        }
+                    }
+                }
+                if (!__syncthreads_or(left)) break;
+                wide_step<K, KW>(P, X, ya, yb, fmv, 0xFFFFFFFFu);
+                wide_screen_override(M, X, ya, yb, 0xFFFFFFFFu);
+                wide_step<K, KW>(P, X, xa, xb, fmv, 0xFFFFFFFFu);
+                wide_screen_override(M, X, xa, xb, 0xFFFFFFFFu);
+                __syncthreads();
+                uint32_t* s = ya; ya = yb; yb = s;
+                s = xa; xa = xb; xb = s;
+                group_steps += 2;
+            }
+            // ---- key: minimum over a lap of lam_max steps from y (on the cycle of every found bit), min in xa
+            cur = ya; nxt = yb;
+            mn = xa;
+            for (uint32_t r = X.r0; r < X.r1; ++r) mn[r * L + c] = cur[r * L + c];
+            for (uint32_t m = 1; m < lam_max; ++m) {
+                wide_step<K, KW>(P, X, cur, nxt, fmv, 0xFFFFFFFFu);
+                wide_screen_override(M, X, cur, nxt, 0xFFFFFFFFu);
+                __syncthreads();
+                uint32_t* s = cur; cur = nxt; nxt = s;
+                ++group_steps;
+                uint32_t lt = 0, eq = 0xFFFFFFFFu;
+                for (uint32_t r = X.r1; r-- > X.r0;) {
+                    const uint32_t v = cur[r * L + c], w = mn[r * L + c];
+                    lt |= eq & ~v & w;
+                    eq &= ~(v ^ w);
+                }
+                red[tid] = lt;
+                red[kWideThreads + tid] = eq;
+                __syncthreads();
+                if (tid < L) {
+                    uint32_t LT = 0, EQ = 0xFFFFFFFFu;
+                    for (uint32_t s2 = nslices; s2-- > 0;) {
+                        LT |= EQ & red[s2 * L + tid];
+                        EQ &= red[kWideThreads + s2 * L + tid];
+                    }
+                    col[L + tid] = LT;
+                }
+                __syncthreads();
+                const uint32_t sel = col[L + c];
+                for (uint32_t r = X.r0; r < X.r1; ++r) mn[r * L + c] = wbfi(sel, cur[r * L + c], mn[r * L + c]);
+            }
+        }
+        __syncthreads();
+        // ---- per-trajectory records of the pair (k < n_valid: bits of a ragged last column stay ST_INVALID, unwritten)
+        for (uint32_t k = tid; k < n_valid; k += kWideThreads) {
+            const uint64_t q = rec0 + k;
+            const bool keep = sta[k] == ST_FOUND && (uint64_t)lam[k] <= P.max_len;
+            P.info[4 * q + 0] = keep ? 1u : 0u;
+            P.info[4 * q + 1] = keep ? lam[k] : 0u;
+            P.info[4 * q + 2] = keep ? mua[k] : 0u;
+            P.info[4 * q + 3] = 0u;
+            for (uint32_t w = 0; w < P.w64; ++w) P.keys[q * P.w64 + w] = keep ? wide_gather64(P, mn, L, k, w) : 0ull;
+        }
+        steps_exec += group_steps * n_valid;
+        __syncthreads();
+    }
+    if (steps_ref) atomicAdd(&P.ctr[0], steps_ref);
+    if (tid == 0 && steps_exec) atomicAdd(&P.ctr[1], steps_exec);
+    if (limit_hits) atomicAdd(&P.ctr[2], limit_hits);
+}
+
+template <int K>
+static hipError_t launch_wide_screen_k(dim3 grid, size_t shmem, hipStream_t st, const WideScreenParams& Q) {
+    const void* fn = Q.net.wdesc ? (const void*)k_wide_screen<K, true> : (const void*)k_wide_screen<K, false>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return e;
+    void* args[] = {const_cast<WideScreenParams*>(&Q)};
+    return hipLaunchKernel(fn, grid, dim3(kWideThreads), args, shmem, st);
+}
+
+hipError_t launch_wide_screen(int k, dim3 grid, size_t shmem, hipStream_t st, const WideScreenParams& Q) {
+    switch (k) {
+        case 1: return launch_wide_screen_k<1>(grid, shmem, st, Q);
+        case 2: return launch_wide_screen_k<2>(grid, shmem, st, Q);
+        case 3: return launch_wide_screen_k<3>(grid, shmem, st, Q);
+        case 4: return launch_wide_screen_k<4>(grid, shmem, st, Q);
+        case 5: return launch_wide_screen_k<5>(grid, shmem, st, Q);
+        case 6: return launch_wide_screen_k<6>(grid, shmem, st, Q);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace bsx

@@ -17,6 +17,11 @@ hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, c
 hipError_t launch_wide_damage(int k, dim3 grid, size_t shmem, hipStream_t st, const WideDamageParams& Q);
 hipError_t launch_wide_trans(int k, dim3 grid, size_t shmem, hipStream_t st, const WideTransParams& Q);
 hipError_t launch_wide_trans_build(const WideTransParams& Q, hipStream_t st);
+hipError_t launch_wide_screen(int k, dim3 grid, size_t shmem, hipStream_t st, const WideScreenParams& Q);
+hipError_t launch_screen_reduce(const uint32_t* info, const uint64_t* keys, uint64_t n_pairs, uint64_t p0, uint64_t g_per, uint64_t n_samples,
+                                uint32_t G, uint32_t w64, ScreenSlot* table, uint64_t slots, unsigned long long* hdr, hipStream_t st);
+hipError_t launch_screen_drain(const ScreenSlot* table, uint64_t slots, ScreenRec* out, uint64_t cap, unsigned long long* hdr,
+                               const unsigned long long* ctr, hipStream_t st);
 hipError_t launch_wide_reduce_attract(const uint32_t* info, const uint64_t* keys, uint64_t m, uint32_t w64, WideSlot* table,
                                       uint64_t slots, unsigned long long* hdr, hipStream_t st);
 hipError_t launch_wide_reduce_drain(const WideSlot* table, uint64_t slots, WideAttrRec* out, uint64_t cap, unsigned long long* hdr,
@@ -34,6 +39,7 @@ struct WideHost {
     DevBuf<uint32_t> d_info, d_thit;
     DevBuf<uint64_t> d_keys;
     DevBuf<WideSlot> d_table;
+    DevBuf<ScreenSlot> d_screen;                // the screen's table (bsx_screen_reduce.hip)
     DevBuf<unsigned long long> d_out, d_hist;   // d_out: kHdrWords header words, then the drained records
 };
 

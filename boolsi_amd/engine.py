@@ -438,6 +438,29 @@ class Engine:
                                                      C.byref(st)))
         return sum_d, sum_d2, merged, cells, st.as_dict()
 
+    def screen_sampled(self, seed, first, count, mutants, max_t=inf, max_len=inf, cap=None):
+        """bsx_run_screen_sampled: a knockout / overexpression screen over samples [first, first + count) of `seed`
+        (include/bsx.h has the definition).  mutants: a list of mutants, each a sequence of (node, value) pairs, the empty
+        one the wild type -> (records per mutant: a list of _lib.ATTR_REC2W arrays in key order, samples without an
+        attractor per mutant: uint64 (len(mutants),), stats)."""
+        mutants = [list(m) for m in mutants]
+        offsets = np.zeros(len(mutants) + 1, np.uint32)
+        offsets[1:] = np.cumsum([len(m) for m in mutants])
+        nodes = np.zeros(max(int(offsets[-1]), 1), _lib.FIXED)
+        for i, (node, value) in enumerate(pair for m in mutants for pair in m):
+            nodes[i] = (int(node), int(value))
+        if cap is None:         # at most one record per trajectory, and never more than the device reduces
+            cap = max(1, min(len(mutants) * int(count), 1 << 20))
+        table = np.zeros(max(int(cap), 1), _lib.SCREEN_REC)
+        none = np.zeros(max(len(mutants), 1), np.uint64)
+        n_out, st = C.c_uint64(), _lib.Stats2()
+        self._check(self._lib.bsx_run_screen_sampled(self._h, int(seed), int(first), int(count), ptr(offsets), ptr(nodes), len(mutants),
+                                                     _cap(max_t), _cap(max_len), ptr(table), int(cap), C.byref(n_out), ptr(none),
+                                                     C.byref(st)))
+        got = table[:n_out.value]
+        cuts = np.searchsorted(got['mutant'], np.arange(len(mutants) + 1, dtype=np.uint64))
+        return [got['rec'][cuts[m]:cuts[m + 1]].copy() for m in range(len(mutants))], none[:len(mutants)], st.as_dict()
+
     def trajectories_sampled(self, seed, samples, t_len):
         """States s(0..t_len[q]) of samples samples[q] of `seed` -> list of (t_len[q] + 1, W) arrays."""
         W = self.net.n_words

@@ -328,6 +328,50 @@ int  bsx_run_damage_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample, 
                             uint32_t n_flips, uint32_t n_steps,
                             uint64_t* sum_d, uint64_t* sum_d2, uint64_t* n_merged, uint64_t* hist, bsx_stats* stats);
 
+/* ---- mutant screens over samples: knockouts and overexpressions in one call (no reference analogue) ----
+ * Which attractors survive, which appear and how do the basin shares move when node v is held at 0 (knockout) or at 1
+ * (overexpression), singly or in combinations?  This definition is NORMATIVE; the notation is that of the sampled source
+ * above.
+ *
+ * A mutant is a list of 0 to BSX_SCREEN_MAX_NODES (node, value) pairs: the nodes distinct, below n and not fixed by the
+ * origin, the values 0 or 1.  The empty list is the wild type.  Mutant m is mut_nodes[mut_offsets[m] .. mut_offsets[m + 1]).
+ * Mutant m over sample j of `seed`:
+ *
+ *   - s(0) is sample j's state of the CURRENT space, exactly as bsx_sample_problems gives it: n_any, the ordinals a and
+ *     the block keys are those of the current space whatever the mutant is, so every mutant runs on the wild type's
+ *     initial states (common random numbers);
+ *   - every listed node behaves as an origin fixed node does (model.py:31-49): it keeps its s(0) value at t = 0 and has
+ *     `value` at every t >= 1;
+ *   - everything else is bsx_run_attract_sampled with T_p = 0: found iff mu + lambda <= max_t, kept iff lambda <= max_len,
+ *     key = the minimum state code over the cycle, l = mu.
+ *
+ * Hence the wild-type mutant gives bsx_run_attract_sampled's records, and a mutant whose nodes all have a constant initial
+ * state gives the records of bsx_run_attract_sampled on the space that lists those nodes under `fixed nodes` (s(0) is NOT
+ * forced: forcing it would break this identity).  The call is a pure function of (seed, first_sample, n_samples, mutant
+ * list); disjoint sample ranges add up, per (mutant, key), to the call over their union.
+ *
+ * table[0 .. *n_out): records sorted by mutant, then by key words from word 0; counts and sums as in bsx_attr_rec2w.
+ * n_no_attractor[m] (nullable) = n_samples - sum of the counts of mutant m.  stats: problems = n_mutants * n_samples, one
+ * host wait (two when more than 256 records come back).  Works on handles of both families (the second lowering of
+ * bsx_run_attract_sampled).  The caller's arrays are written only by a call that succeeds; n_samples == 0 is BSX_OK with
+ * zeros written.  Reduced on the device only (BSX_WIDE_HOST_REDUCE is not read).
+ *
+ * Checked before anything is launched:  BSX_ERR_STATE without a network or a problem space;  BSX_ERR_INVALID if
+ * first_sample + n_samples wraps, an array is NULL, the offsets do not ascend from 0, a mutant is longer than
+ * BSX_SCREEN_MAX_NODES, a node is >= n, repeated within its mutant or fixed by the origin, a value is above 1, n_mutants is
+ * 0 or above BSX_SCREEN_MAX_MUTANTS (the text names the mutant and the node);  BSX_ERR_UNSUPPORTED for a space with
+ * fixed-node variations, perturbation variations or an origin perturbation schedule (the text says which);
+ * BSX_ERR_RANGE_TOO_LARGE if n_mutants * n_samples exceeds 2^40;  BSX_ERR_TABLE_FULL for more distinct (mutant, key) pairs
+ * than min(cap, 2^20). */
+#define BSX_SCREEN_MAX_NODES   4
+#define BSX_SCREEN_MAX_MUTANTS (1u << 20)
+typedef struct { uint64_t mutant; bsx_attr_rec2w rec; } bsx_screen_rec;
+int  bsx_run_screen_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample, uint64_t n_samples,
+                            const uint32_t* mut_offsets /* [n_mutants + 1] */, const bsx_fixed* mut_nodes,
+                            uint32_t n_mutants, uint64_t max_t, uint64_t max_len,
+                            bsx_screen_rec* table, uint64_t cap, uint64_t* n_out,
+                            uint64_t* n_no_attractor /* [n_mutants], nullable */, bsx_stats2* stats);
+
 /* target (target.py:109-133): hits in ascending offset order into hits[0..*n_hits); mask/code are W words
  * (target node set / target substate code, input.py:580-661). */
 int  bsx_run_target(bsx_handle h, const bsx_index* first, uint64_t count, uint64_t max_t,
