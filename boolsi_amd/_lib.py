@@ -26,6 +26,7 @@ EXPORTS = (
     'bsx_run_target_summary', 'bsx_run_simulate', 'bsx_run_trajectories', 'bsx_run_attractor_profile', 'bsx_run_node_correlations', 'bsx_run_attractor_transitions', 'bsx_run_attractor_transitions_wide',
     'bsx_run_attract_sampled', 'bsx_sample_problems',
     'bsx_run_target_sampled', 'bsx_run_simulate_sampled', 'bsx_run_trajectories_sampled', 'bsx_run_damage_sampled', 'bsx_run_screen_sampled',
+    'bsx_run_influence_sampled',
     'bsx_synchronize',
     'bsx_comm_unique_id', 'bsx_comm_init', 'bsx_comm_allgather', 'bsx_comm_destroy',
 )
@@ -37,6 +38,7 @@ TRANS_OUTSIDE = 0xFFFFFFFE  # BSX_TRANS_OUTSIDE
 TRANS_UNRESOLVED = 0xFFFFFFFF   # BSX_TRANS_UNRESOLVED
 SCREEN_MAX_NODES = 4        # BSX_SCREEN_MAX_NODES
 SCREEN_MAX_MUTANTS = 1 << 20    # BSX_SCREEN_MAX_MUTANTS
+INFLUENCE_MAX_CELLS = 1 << 26   # BSX_INFLUENCE_MAX_CELLS
 
 
 class EngineUnavailable(RuntimeError):
@@ -160,6 +162,7 @@ def load():
     lib.bsx_run_trajectories_sampled.argtypes = [vp, u64, vp, vp, u64, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_damage_sampled.argtypes = [vp, u64, u64, u64, u32, u32, vp, vp, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_screen_sampled.argtypes = [vp, u64, u64, u64, vp, vp, u32, u64, u64, vp, u64, C.POINTER(u64), vp, C.POINTER(Stats2)]
+    lib.bsx_run_influence_sampled.argtypes = [vp, u64, u64, u64, vp, u32, u32, vp, vp, C.POINTER(Stats)]
     lib.bsx_run_attract_fgraph.argtypes = [vp, C.POINTER(Index), u64, u64, u64, vp, u32, C.POINTER(u32),
                                            C.POINTER(u64), C.POINTER(Stats)]
     lib.bsx_run_target.argtypes = [vp, C.POINTER(Index), u64, u64, vp, vp, vp, u64, C.POINTER(u64),

@@ -1,7 +1,7 @@
 """
 Command line: `python -m boolsi_amd simulate|attract|target FILE [options]`, same commands and
-option names as the reference's `boolsi` script (`boolsi/cli.py:35-63, 184-328`), and `damage` and `screen`, which the
-reference does not have (boolsi_amd/damage.py, boolsi_amd/screen.py).
+option names as the reference's `boolsi` script (`boolsi/cli.py:35-63, 184-328`), and `damage`, `screen` and `influence`, which the
+reference does not have (boolsi_amd/damage.py, boolsi_amd/screen.py, boolsi_amd/influence.py).
 
 Differences, all outside the hot path: results are kept in memory instead of a ZODB spill
 (`-d`, `-k` accepted and ignored); `-b` does not schedule anything (the GPU dequeues its own chunks),
@@ -370,6 +370,54 @@ def screen(**kw):
                                      cfg['incoming node lists'], cfg['truth tables'], kw['samples'], kw['seed'] or 0, mutants,
                                      kw['max_simulation_time'] or inf, kw['max_attractor_length'] or inf)
         output_screen(tables, none, mutants, cfg['node names'], kw['samples'], run.out)
+    _guarded(kw, body)
+
+
+def _influence_sources(kw):
+    """The source list of `influence`, from the input's node names and fixed nodes alone: a usage error where it cannot be
+    built.  An input that does not parse is left to the run itself, which reports it the usual way."""
+    from .influence import InfluenceUsageError, build_sources
+    from .input import parse_input
+    logging.disable(logging.CRITICAL)
+    try:
+        cfg = parse_input(kw['input_file'], kw['simulation_time'], Mode.ATTRACT)
+    except Exception:   # noqa: BLE001
+        return None
+    finally:
+        logging.disable(logging.NOTSET)
+    names = None if kw['nodes'] is None else [name.strip() for name in kw['nodes'].split(',')]
+    try:
+        return build_sources(cfg['node names'], cfg['origin simulation problem'][1], names)
+    except InfluenceUsageError as e:
+        raise click.UsageError(str(e))
+
+
+@cli.command(help='Measure which node\'s inversion reaches which node, and when: the influence matrix over sampled '
+                  'initial conditions.')
+@_common
+@click.option('-t', '--simulation-time', type=click.IntRange(min=1, max=65535), required=True,
+              help='(required) Number of time steps to follow every inverted node for.')
+@click.option('--samples', 'samples', type=click.IntRange(min=1, max=2 ** 31),
+              help='(required) Number of sampled initial conditions; every source node is inverted in each of them.')
+@_seed_option
+@click.option('--nodes', 'nodes', default=None,
+              help='Names of the source nodes, comma-separated. Defaults to every node the input does not fix.')
+def influence(**kw):
+    _check_sampling(kw)
+    if kw['samples'] is None:
+        raise click.UsageError('influence needs --samples: initial conditions are sampled, never enumerated.')
+    sources = _influence_sources(kw)
+
+    def body(run):
+        from .influence import influence_master, output_influence
+        if run.comm.world > 1:
+            logging.getLogger().error('The influence command runs on one GPU; multi-rank runs are not supported.')
+            return
+        cfg = run.read_input(kw['simulation_time'], Mode.ATTRACT)
+        table, merged = influence_master(run.open_engine(), cfg['origin simulation problem'], cfg['simulation problem variations'],
+                                         cfg['incoming node lists'], cfg['truth tables'], kw['samples'], kw['seed'] or 0,
+                                         kw['simulation_time'], sources)
+        output_influence(table, merged, sources, cfg['node names'], kw['samples'], run.out)
     _guarded(kw, body)
 
 

@@ -133,6 +133,29 @@ inline uint32_t wide_damage_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslo
            6 * acc_steps;
 }
 
+// ---- node influence (k_wide_influence in bsx_wide.hip, bsx_run_influence_sampled; include/bsx.h has the definition,
+// bsx_influence.h the layout) ----
+// The work items of a launch are (source, group) pairs p = p0 + i, i < n_items: group p % g_per of source p / g_per, its
+// samples first_sample + 32 L * group + k of the sampled source.  X (matrices 0 / 1) and Y (matrices 2 / 3) as in damage,
+// Y = X with row sources[source] inverted under the columns' valid-bits masks.  After a lock step the count of row i is the
+// popcount of X[i] ^ Y[i] over the L columns: one LDS counter per row, touched only for a nonzero word, and flushed with
+// one 32-bit global add per nonzero (source, t, row).  `net` carries the network part, origin, any_nodes /
+// n_any, sample_k0 and ctr; the space has no variations and no schedule (the host refuses the others).
+struct WideInfluenceParams {
+    WideParams net;
+    uint64_t first_sample, n_samples;
+    uint64_t p0, n_items, g_per;
+    uint32_t n_steps, pad;
+    const uint32_t* sources;        // [n_sources]
+    uint32_t* influence;            // [n_sources][n_steps][n_nodes], zeroed by the host
+    unsigned long long* n_merged;   // nullable: [n_sources][n_steps], zeroed by the host
+};
+// LDS words of k_wide_influence: four matrices, the (zero) fixed-variation masks, the row counters and the per-column ORs
+// of a step (both in two halves, by the step's parity), the block keys of the columns.
+inline uint32_t wide_influence_lds_words(uint32_t rows, uint32_t L, uint32_t n_fslots) {
+    return kWideBuffers * rows * L + 2 * n_fslots * L + 2 * rows + 2 * L + 4 * L + 8;
+}
+
 // ---- attractor transitions (k_wide_trans / k_wide_trans_build in bsx_wide.hip, bsx_run_attractor_transitions_wide) ----
 // A group of 32 * L trajectories runs k_wide's attract phases (Brent in lock step, the mu pass, the key lap) with
 // T_p = 0 and the origin's fixed nodes only.  Two kinds of source:

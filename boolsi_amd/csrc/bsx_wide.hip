@@ -12,10 +12,12 @@
 // k_wide<K, KW, true> (attract) and k_wide<K, KW, true, MODE> (target, simulate) run over samples of a seed instead of
 // consecutive problem indices (bsx_sample.h): the same body, with the group's set-up and the one branch an instantiation
 // carries chosen at compile time.  k_wide_screen (at the end of the file) runs the attract phases per (mutant, group)
-// pair of a knockout / overexpression screen over samples.
+// pair of a knockout / overexpression screen over samples; k_wide_influence (behind k_wide_damage) counts, per (source,
+// group) pair, which rows differ after a single node was inverted.
 #include <hip/hip_runtime.h>
 
 #include "bsx_device.h"
+#include "bsx_influence.h"
 #include "bsx_planes.h"
 #include "bsx_sample.h"
 #include "bsx_screen.h"
@@ -992,6 +994,159 @@ hipError_t launch_wide_damage(int k, dim3 grid, size_t shmem, hipStream_t st, co
         case 4: return launch_wide_damage_k<4>(grid, shmem, st, Q);
         case 5: return launch_wide_damage_k<5>(grid, shmem, st, Q);
         case 6: return launch_wide_damage_k<6>(grid, shmem, st, Q);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Node influence (bsx_run_influence_sampled; include/bsx.h has the definition, bsx_wide.h / bsx_influence.h the layout).
+// A workgroup's work items are (source, group) pairs: damage's set-up with one row of Y inverted instead of drawn flips,
+// then per lock step two wide_step calls and the counts of X ^ Y per row.
+//
+// Counts.  Behind the step every thread holds the words it has just written for its owned rows of its column; row r of a
+// slice lies in the L adjacent lanes of that slice.  Most rows are zero in an ordered network, so a lane does nothing for
+// a zero word and adds the popcount of a nonzero one to the row's LDS counter: up to L adders on one address, which the
+// LDS serialises.  (BSX_INFLUENCE_COUNTS = 1 builds the alternative: one ballot per row, and where a wave holds a nonzero
+// word the popcounts summed over the slice's L lanes by shuffles, then one adder per row.  It measured 9 to 25 % slower,
+// DESIGN.md "Node influence" in section 5 has the figures; 0 compiles the count stage out.  Both are for measurements only.)
+// The counters and the per-column ORs come in two halves by the parity of t: a step's half is flushed and cleared behind
+// the step's barrier, while the next step already adds to the other half, so a lock step has one barrier.
+#if !defined(BSX_INFLUENCE_COUNTS)
+#define BSX_INFLUENCE_COUNTS 2
+#endif
+
+template <int K, bool KW>
+__global__ __launch_bounds__(kWideThreads) void k_wide_influence(const WideInfluenceParams Q) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
+    const WideParams& P = Q.net;
+    WideCtx X;
+    X.L = P.L;
+    X.tid = threadIdx.x;
+    X.c = X.tid & (P.L - 1);
+    X.slice = X.tid >> P.lshift;
+    X.r0 = X.slice * P.rows_ps;
+    X.r1 = X.r0 + P.rows_ps;
+    X.RL = P.rows * P.L;
+    const uint32_t L = P.L, c = X.c, RL = X.RL, G = 32 * L, tid = X.tid;
+    const uint32_t T = Q.n_steps, n = P.n_nodes;
+    uint32_t* B[4] = {sm, sm + RL, sm + 2 * RL, sm + 3 * RL};       // X: 0 / 1, Y: 2 / 3
+    uint32_t* fmv = sm + 4 * RL;                    // [n_fslots][2][L]  all zero: no variations here
+    uint32_t* cnt = fmv + 2 * P.n_fslots * L;       // [2][rows]         counts of step t in half t & 1; zero between steps
+    uint32_t* colv = cnt + 2 * P.rows;              // [2][L]            OR of the column's diff words, likewise
+    uint32_t* keys = colv + 2 * L;                  // [L][4]            block keys of the columns
+    unsigned long long steps_exec = 0;
+    for (uint32_t i = tid; i < 2 * P.n_fslots * L; i += kWideThreads) fmv[i] = 0;
+    for (uint32_t i = tid; i < 2 * P.rows + 2 * L; i += kWideThreads) cnt[i] = 0;
+
+    for (uint64_t pi = blockIdx.x; pi < Q.n_items; pi += gridDim.x) {
+        const InfluenceItem item = influence_item_of(Q.p0 + pi, Q.g_per, Q.n_samples, G);
+        const uint32_t n_valid = item.n_valid;
+        const uint64_t j_first = Q.first_sample + item.first;               // the group's first sample
+        const uint32_t src = Q.sources[item.source];                        // uniform: a scalar load
+        const size_t row0 = (size_t)item.source * T;                        // row (source, t) of the tables is row0 + t - 1
+        // ---- x(0) = y(0) = origin | 'any' words of the sampled source (damage's set-up)
+        for (uint32_t i = tid; i < RL; i += kWideThreads) {
+            const uint32_t r = i >> P.lshift;
+            B[0][i] = B[2][i] = (r < n && ((P.origin[r >> 5] >> (r & 31u)) & 1u)) ? 0xFFFFFFFFu : 0u;
+        }
+        if (tid < L) {
+            const SampleColumn sc = sample_column(P.sample_k0, j_first + 32ull * tid);
+            keys[4 * tid + 0] = (uint32_t)sc.kb0; keys[4 * tid + 1] = (uint32_t)(sc.kb0 >> 32);
+            keys[4 * tid + 2] = (uint32_t)sc.kb1; keys[4 * tid + 3] = (uint32_t)(sc.kb1 >> 32);
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < P.n_any * L; i += kWideThreads) {
+            const uint32_t a = i >> P.lshift, cw = i & (L - 1);
+            const SampleColumn sc = wide_sample_column(keys, cw, j_first + 32ull * cw);
+            const uint32_t n_bits = n_valid > 32 * cw ? (n_valid - 32 * cw < 32u ? n_valid - 32 * cw : 32u) : 0u;
+            const uint32_t word = sample_column_word(sc, a, n_bits);
+            B[0][P.any_nodes[a] * L + cw] = word;
+            B[2][P.any_nodes[a] * L + cw] = word;
+        }
+        __syncthreads();
+        // ---- y(0): row `src` inverted in the valid bits of every column; the bits behind the end of a ragged group stay
+        // equal in X and Y, and so are never counted
+        uint32_t valid = 0;                         // of column tid (tid < L)
+        if (tid < L) {
+            const uint32_t n_bits = n_valid > 32 * tid ? (n_valid - 32 * tid < 32u ? n_valid - 32 * tid : 32u) : 0u;
+            valid = n_bits >= 32u ? 0xFFFFFFFFu : (1u << n_bits) - 1u;
+            B[2][src * L + tid] ^= valid;
+        }
+        __syncthreads();
+        uint32_t *xc = B[0], *xn = B[1], *yc = B[2], *yn = B[3];
+        uint32_t group_steps = 0;
+        for (uint32_t t = 1; t <= T; ++t) {
+            uint32_t* ct = cnt + (t & 1u) * P.rows;
+            uint32_t* cv = colv + (t & 1u) * L;
+            wide_step<K, KW>(P, X, xc, xn, fmv, 0xFFFFFFFFu);
+            wide_step<K, KW>(P, X, yc, yn, fmv, 0xFFFFFFFFu);
+            ++group_steps;
+            // ---- the rows this thread has just written: OR of the diff words, counts of the nonzero ones
+            uint32_t orv = 0;
+            for (uint32_t r = X.r0; r < X.r1; ++r) {
+                const uint32_t d = xn[r * L + c] ^ yn[r * L + c];
+                orv |= d;
+#if BSX_INFLUENCE_COUNTS == 1
+                if (__builtin_amdgcn_ballot_w64(d != 0u)) {
+                    uint32_t s = (uint32_t)__builtin_popcount(d);
+                    for (uint32_t off = 1; off < L && off < 64u; off <<= 1) s += __shfl_xor(s, (int)off);
+                    if ((c & 63u) == 0 && s) atomicAdd(&ct[r], s);      // (L > 64: a row spans waves, hence an add, not a store)
+                }
+#elif BSX_INFLUENCE_COUNTS == 2
+                if (d) atomicAdd(&ct[r], (uint32_t)__builtin_popcount(d));
+#endif
+            }
+            if (orv) atomicOr(&cv[c], orv);
+            const bool alive = __syncthreads_or(orv != 0u);
+            // ---- flush: one global add per nonzero (source, t, row); merged = the valid bits that no row has set
+            uint32_t* out = Q.influence + (row0 + t - 1) * n;
+            for (uint32_t i = tid; i < n; i += kWideThreads) {
+                const uint32_t v = ct[i];
+                if (v) { atomicAdd(&out[i], v); ct[i] = 0; }
+            }
+            if (Q.n_merged) {
+                uint32_t mg = 0;
+                if (tid < L) { mg = (uint32_t)__builtin_popcount(valid & ~cv[tid]); cv[tid] = 0; }
+                if (tid < ((L + 63u) & ~63u)) {         // the waves that hold a column: whole waves, so the shuffles are uniform
+#pragma unroll
+                    for (int off = 32; off >= 1; off >>= 1) mg += __shfl_xor(mg, off);
+                    if ((tid & 63u) == 0 && mg) atomicAdd(&Q.n_merged[row0 + t - 1], (unsigned long long)mg);
+                }
+            } else if (tid < L) {
+                cv[tid] = 0;
+            }
+            if (!alive) {
+                // every pair of the group has merged, and merged pairs stay merged: nothing differs from here on
+                if (Q.n_merged)
+                    for (uint32_t t2 = t + 1 + tid; t2 <= T; t2 += kWideThreads) atomicAdd(&Q.n_merged[row0 + t2 - 1], (unsigned long long)n_valid);
+                break;
+            }
+            uint32_t* s = xc; xc = xn; xn = s;
+            s = yc; yc = yn; yn = s;
+        }
+        steps_exec += 2ull * group_steps * n_valid;
+        __syncthreads();
+    }
+    if (tid == 0 && steps_exec) atomicAdd(&P.ctr[1], steps_exec);
+}
+
+template <int K>
+static hipError_t launch_wide_influence_k(dim3 grid, size_t shmem, hipStream_t st, const WideInfluenceParams& Q) {
+    const void* fn = Q.net.wdesc ? (const void*)k_wide_influence<K, true> : (const void*)k_wide_influence<K, false>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e != hipSuccess) return e;
+    void* args[] = {const_cast<WideInfluenceParams*>(&Q)};
+    return hipLaunchKernel(fn, grid, dim3(kWideThreads), args, shmem, st);
+}
+
+hipError_t launch_wide_influence(int k, dim3 grid, size_t shmem, hipStream_t st, const WideInfluenceParams& Q) {
+    switch (k) {
+        case 1: return launch_wide_influence_k<1>(grid, shmem, st, Q);
+        case 2: return launch_wide_influence_k<2>(grid, shmem, st, Q);
+        case 3: return launch_wide_influence_k<3>(grid, shmem, st, Q);
+        case 4: return launch_wide_influence_k<4>(grid, shmem, st, Q);
+        case 5: return launch_wide_influence_k<5>(grid, shmem, st, Q);
+        case 6: return launch_wide_influence_k<6>(grid, shmem, st, Q);
         default: return hipErrorInvalidValue;
     }
 }

@@ -15,6 +15,7 @@ hipError_t launch_wide_sampled(int k, dim3 grid, size_t shmem, hipStream_t st, c
 hipError_t launch_sample_problems(const WideSampleListParams& Q, hipStream_t st);
 hipError_t launch_wide_profile(int k, dim3 grid, size_t shmem, hipStream_t st, const WideProfileParams& Q);
 hipError_t launch_wide_damage(int k, dim3 grid, size_t shmem, hipStream_t st, const WideDamageParams& Q);
+hipError_t launch_wide_influence(int k, dim3 grid, size_t shmem, hipStream_t st, const WideInfluenceParams& Q);
 hipError_t launch_wide_trans(int k, dim3 grid, size_t shmem, hipStream_t st, const WideTransParams& Q);
 hipError_t launch_wide_trans_build(const WideTransParams& Q, hipStream_t st);
 hipError_t launch_wide_screen(int k, dim3 grid, size_t shmem, hipStream_t st, const WideScreenParams& Q);

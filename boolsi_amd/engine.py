@@ -461,6 +461,20 @@ class Engine:
         cuts = np.searchsorted(got['mutant'], np.arange(len(mutants) + 1, dtype=np.uint64))
         return [got['rec'][cuts[m]:cuts[m + 1]].copy() for m in range(len(mutants))], none[:len(mutants)], st.as_dict()
 
+    def influence_sampled(self, seed, first, count, sources, n_steps, merged=True):
+        """bsx_run_influence_sampled: the influence matrix over samples [first, first + count) of `seed` (include/bsx.h has
+        the definition).  sources: distinct nodes the origin does not fix, in any order -> (influence: uint32 (n_sources,
+        n_steps, n), the samples in which the target differs at t = 1 .. n_steps after the source was inverted at t = 0;
+        n_merged: uint64 (n_sources, n_steps) or None; stats)."""
+        src = np.ascontiguousarray(sources, np.uint32)
+        n_steps = int(n_steps)
+        table = np.zeros((len(src), n_steps, self.net.n_nodes), np.uint32)
+        gone = np.zeros((len(src), n_steps), np.uint64) if merged else None
+        st = Stats()
+        self._check(self._lib.bsx_run_influence_sampled(self._h, int(seed), int(first), int(count), ptr(src), len(src), n_steps,
+                                                        ptr(table), ptr(gone) if merged else None, C.byref(st)))
+        return table, gone, st.as_dict()
+
     def trajectories_sampled(self, seed, samples, t_len):
         """States s(0..t_len[q]) of samples samples[q] of `seed` -> list of (t_len[q] + 1, W) arrays."""
         W = self.net.n_words

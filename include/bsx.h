@@ -328,6 +328,40 @@ int  bsx_run_damage_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample, 
                             uint32_t n_flips, uint32_t n_steps,
                             uint64_t* sum_d, uint64_t* sum_d2, uint64_t* n_merged, uint64_t* hist, bsx_stats* stats);
 
+/* ---- node influence over samples: which node's flip reaches which node, and when (no reference analogue) ----
+ * The influence matrix I(v -> i, t) = P(node i differs at step t | node v was inverted at step 0).  Its t = 1 slice is the
+ * classical activity / influence of the rules, its row sums are the per-node sensitivities, its overall mean is the first
+ * point of the Derrida curve; later slices show signalling range and the nodes whose perturbation never dies.  This
+ * definition is NORMATIVE; the notation is that of the sampled source above, `free` is the ascending list of the nodes the
+ * origin does not fix, as in damage.  A call lists n_sources distinct free nodes sources[s], in any order.  For source s
+ * and sample j of `seed`, T = n_steps:
+ *
+ *   - x(0) is sample j's state, exactly as bsx_sample_problems gives it; y(0) is x(0) with node sources[s] inverted.  No
+ *     random draw is involved;
+ *   - x(t+1) = F(x(t)), y(t+1) = F(y(t)) under the network's rules and the origin's fixed nodes only;
+ *   - D_j(t) = x(t) ^ y(t) for t = 1 .. T.
+ *
+ * Over samples [first_sample, first_sample + n_samples):
+ *   influence[(s * T + (t - 1)) * n_nodes + i] = the number of samples with bit i of D_j(t) set;
+ *   n_merged[s * T + (t - 1)] (nullable)       = the number of samples with D_j(t) == 0.
+ * t = 0 is not stored: it is n_samples at i = sources[s] and 0 elsewhere.  A pure function of (seed, first_sample,
+ * n_samples, sources, n_steps); disjoint sample ranges add up cell by cell; row s depends on sources[s] alone, so a call
+ * over a subset or a permutation of the sources gives the same rows.  Works on handles of both families (the second
+ * lowering of bsx_run_attract_sampled).  The arrays are written only by a call that succeeds; n_samples == 0 is BSX_OK with
+ * zeros written.  stats: problems = n_sources * n_samples, state_steps = 2 * n_sources * n_samples * T, executed_steps =
+ * the updates that ran (a group whose every pair has merged stops stepping: merged pairs stay merged); one host wait.
+ *
+ * Checked, in this order, before anything is launched:  BSX_ERR_STATE without a network or a problem space;
+ * BSX_ERR_INVALID if influence or sources is NULL, n_sources or n_steps is 0, first_sample + n_samples wraps, or a source
+ * is >= n, repeated or fixed by the origin (the text names the entry and the node);  BSX_ERR_RANGE_TOO_LARGE for n_samples
+ * > 2^31 (a cell has 32 bits) or n_sources * n_samples > 2^40;  BSX_ERR_UNSUPPORTED for more than BSX_INFLUENCE_MAX_CELLS
+ * cells (n_sources * T * n_nodes);  BSX_ERR_UNSUPPORTED for a space with fixed-node variations, perturbation variations or
+ * an origin perturbation schedule (the text says which). */
+#define BSX_INFLUENCE_MAX_CELLS (1ull << 26)
+int  bsx_run_influence_sampled(bsx_handle h, uint64_t seed, uint64_t first_sample, uint64_t n_samples,
+                               const uint32_t* sources, uint32_t n_sources, uint32_t n_steps,
+                               uint32_t* influence, uint64_t* n_merged /* nullable */, bsx_stats* stats);
+
 /* ---- mutant screens over samples: knockouts and overexpressions in one call (no reference analogue) ----
  * Which attractors survive, which appear and how do the basin shares move when node v is held at 0 (knockout) or at 1
  * (overexpression), singly or in combinations?  This definition is NORMATIVE; the notation is that of the sampled source
